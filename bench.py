@@ -18,10 +18,14 @@ N > 1 GPUs (weak scaling: 2048 rows per GPU per step), ``--parallelism``:
       mechanism); each chunk's kernels replay from HIP graphs.
   zero1  data parallel with ZeRO-1: reduce-scatter of the gradients onto row owners, Adam on
       the owned rows only, all-gather of the bf16 shadows (parallel/zero.py).
-The run times the other strategy too (untimed for the headline) and reports it under
-``alt_parallelism`` in the JSON line.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+what the headline figure does not need: the FVU@L0 evaluation (after training on, untimed, to
+``--quality-steps``) and, at N > 1, the cross-rank consistency checks and a timed run of the
+other strategy (reported under ``alt_parallelism`` in the JSON line).  ``--dump-outputs DIR``
+writes what the last timed step left (losses and parameters) as ``DIR/<name>.npy``.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N bench.py --gpus N ...
 Prints one JSON line (rank 0).
 """
@@ -59,6 +63,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the FVU@L0 evaluation after training "
+                         "on (untimed) to --quality-steps, and at N > 1 the cross-rank consistency checks and the "
+                         "timed run of the other parallelism strategy (--no-eval / --compare-parallelism 0 still "
+                         "switch these off one by one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left -- the per-model losses and "
+                         "the trained parameters -- as DIR/<name>.npy (float32; at most 64 MB in all: a larger "
+                         "array is cut to a fixed, seeded sample of its elements)")
     ap.add_argument("--batch", type=int, default=2048, help="rows per GPU per step")
     ap.add_argument("--d", type=int, default=512)
     ap.add_argument("--ratio", type=int, default=4)
@@ -148,6 +161,35 @@ def fvu_l0(dicts, x):
     return [(float(mean_l0(ld, x)), float(fraction_variance_unexplained(ld, x))) for ld in dicts]
 
 
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(arrays, where, write=True, budget=DUMP_BYTES):
+    """``--dump-outputs``: each tensor of ``arrays`` (name -> tensor) as ``where/<name>.npy``, float64
+    tensors as float64 and everything else as float32.  When all of them exceed ``budget`` bytes, every
+    array above an equal share of it is cut to that share: a sorted sample of its flattened elements
+    drawn with a fixed seed (the same indices in every run at the same shapes).  Returns what was
+    written: name -> [full shape, elements kept]."""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    share = budget // max(1, len(host))
+    fits = sum(a.nbytes for a in host.values()) <= budget
+    written = {}
+    if write:
+        os.makedirs(where, exist_ok=True)
+    for name, a in host.items():
+        shape = list(a.shape)
+        if not fits and a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        written[name] = [shape, int(a.size)]
+        if write:
+            np.save(os.path.join(where, f"{name}.npy"), a)
+    return written
+
+
 # single-GPU fused step: at most this many optimizer steps per HIP graph replay (each replay
 # boundary costs an ~9 us idle gap on MI355X); engine/graph_plan.py picks the tiling with the fewest
 # timed replays -- the warmup replays the timed graphs first only when it is long enough
@@ -161,10 +203,13 @@ class Runner:
     ``setup(tiling)``: capture (and upload) every graph the run will replay -- before warmup;
     ``run(groups)``: one full optimizer step per entry of ``sum(groups)``, replayed as one graph per
     group where the runner has graphs; ``finish()``: complete cross-step work in flight;
-    ``dicts()``: LearnedDicts; ``close()``."""
+    ``dicts()``: LearnedDicts; ``outputs()``: name -> tensor of what the last step left for its
+    caller (default: every tensor of the LearnedDicts; collective where ``dicts()`` is); ``close()``."""
 
-    def __init__(self, step, dicts, finish=None, close=None, run=None, setup=None):
+    def __init__(self, step, dicts, finish=None, close=None, run=None, setup=None, outputs=None):
         self.step, self.dicts = step, dicts
+        self.outputs = outputs or (lambda: {f"model{i}_{k}": v for i, ld in enumerate(dicts())
+                                            for k, v in sorted(vars(ld).items()) if torch.is_tensor(v)})
         self.path, self.comm, self.consistency = "single", None, None
         self.fallback = None  # why the in-graph path was abandoned for host-issued collectives
         self.finish = finish or (lambda: None)
@@ -334,12 +379,16 @@ def make_runner(par, args, info, sig, models, ring, device, grad_dtype, dist_gra
         from sparse_coding__amd.engine.graph_plan import count_pattern
 
         eng = FusedSAEEnsemble(models, sig, lr=1e-3, batch_size=B, device=device, grad_dtype=args.wgrad_dtype)
+
+        def outputs():  # what step_batch / step_source hand back ([G, 6] losses) and the stacked fp32 masters
+            return {"losses": eng.out, **eng.params}
+
         if args.no_graph:
             def step():
                 ring.sample_shard(B, 0, 1, out=eng.x_static)
                 eng.step_batch(eng.x_static)
 
-            return Runner(step, lambda: eng.to_learned_dicts(device))
+            return Runner(step, lambda: eng.to_learned_dicts(device), outputs=outputs)
         # every step (ring batch gather included) runs from HIP graphs of up to GRAPH_STEPS steps;
         # feature counts are sampled on the first step of each replay (every <= 8 steps)
         eng.enable_graph().attach_source(ring.graph_source(B))
@@ -351,7 +400,7 @@ def make_runner(par, args, info, sig, models, ring, device, grad_dtype, dist_gra
         def setup(tiling):
             eng.prime_source(patterns=[count_pattern(s, GRAPH_STEPS) for s in tiling.sizes])
 
-        return Runner(lambda: run([1]), lambda: eng.to_learned_dicts(device), run=run, setup=setup)
+        return Runner(lambda: run([1]), lambda: eng.to_learned_dicts(device), run=run, setup=setup, outputs=outputs)
     from sparse_coding__amd.engine.ensemble import FunctionalEnsemble
     from sparse_coding__amd.engine.optim import adam
     from sparse_coding__amd.parallel.data_parallel import DataParallelEnsemble
@@ -901,7 +950,12 @@ def main(argv=None):
     quality = None
     trained = args.warmup + args.steps
     wd.arm("eval", WATCHDOG_S["eval"])
-    if not args.no_eval:
+    dumped = None
+    if args.dump_outputs:  # before any further (untimed) training: the state the last timed step left
+        runner.finish()
+        torch.cuda.synchronize()
+        dumped = dump_outputs(runner.outputs(), args.dump_outputs, write=info.is_main)
+    if args.full and not args.no_eval:
         if trained < args.quality_steps:  # untimed: train on toward convergence before evaluating
             from sparse_coding__amd.engine.graph_plan import chunks
 
@@ -917,7 +971,7 @@ def main(argv=None):
     # cross-rank check of the run just timed (collective): replicas identical (dp / zero1) or the same
     # global batches on every rank (es)
     wd.arm("checks", WATCHDOG_S["checks"])
-    consistency = runner.consistency() if distributed and runner.consistency is not None else None
+    consistency = runner.consistency() if args.full and distributed and runner.consistency is not None else None
     devices = rank_devices(info, runner.comm)
     rccl_ranks = runner.comm.count() if runner.comm is not None and hasattr(runner.comm, "count") else None
     runner.close()
@@ -929,6 +983,8 @@ def main(argv=None):
             "value": round(value, 1),
             "unit": "activations/s",
             "n_gpus": info.world_size,
+            "full": args.full,
+            "dumped_outputs": dumped,
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms, 4),
@@ -994,7 +1050,7 @@ def main(argv=None):
     # N > 1: also time the other multi-GPU strategy on the same models (untimed for the
     # headline; reported under "alt_parallelism" so both the gradient all-reduce path --
     # BASELINE config 3's mechanism -- and the ensemble-sharded path are on record)
-    if distributed and args.compare_parallelism and args.models % info.world_size == 0:
+    if args.full and distributed and args.compare_parallelism and args.models % info.world_size == 0:
         other = "dp" if par in ("es", "zero1") else "es"
         alt_models = [sig.init(args.d, n, float(l1), device=device) for l1 in l1s]
         alt = {"parallelism": f"{other}{info.world_size}",

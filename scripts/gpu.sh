@@ -8,7 +8,7 @@
 #   tests      pytest -m gpu (all GPU tests, one process)
 #   kernels    pytest tests/test_kernels_gpu.py only
 #   smoke      __graft_entry__.smoke()
-#   bench      bench.py --steps 50 --warmup 10 (JSON -> gpurun_out/bench.json)
+#   bench      bench.py --full --steps 50 --warmup 10 (JSON -> bench.json in the output folder)
 #   eager      bench.py --engine eager (same-box PyTorch eager baseline)
 #   prof       rocprofv3 --kernel-trace --stats of bench.py (summary -> gpurun_out/prof_summary.txt)
 #   pmc        three rocprofv3 --pmc passes over scripts/prof_step_kernels.py
@@ -44,7 +44,7 @@ run_step() {
     smoke)
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1; local rc=$?; cat "$O/smoke.log"; return $rc ;;
     bench)
-      timeout -k 10 400 python bench.py --steps 50 --warmup 10 ${BENCH_ARGS} > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; return 1; }
+      timeout -k 10 400 python bench.py --full --steps 50 --warmup 10 ${BENCH_ARGS} > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; return 1; }
       cat "$O/bench.json" ;;
     eager)
       timeout -k 10 400 python bench.py --engine eager --steps 20 --warmup 5 --no-eval ${BENCH_ARGS} > "$O/bench_eager.json" 2> "$O/bench_eager.err" || { tail -20 "$O/bench_eager.err"; return 1; }

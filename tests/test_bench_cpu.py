@@ -43,6 +43,42 @@ def test_main_fails_fast_without_enough_gpus(monkeypatch):
     assert launched and launched[0][0] == 8 and "--steps" in launched[0][1]
 
 
+def test_full_and_dump_outputs_are_off_by_default():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    a = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_keeps_dtypes_budget_and_a_fixed_sample(tmp_path):
+    """Everything fits: written whole (float64 stays, bf16 becomes float32).  Over the budget: only the
+    arrays above an equal share are cut, to the same sorted seeded sample in every call."""
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(3)
+    arrays = {"big": torch.randn(4, 1000, generator=g), "small": torch.randn(10, generator=g).to(torch.bfloat16),
+              "wide": torch.randn(3, generator=g, dtype=torch.float64)}
+    got = bench.dump_outputs(arrays, str(tmp_path / "a"))
+    assert got == {"big": [[4, 1000], 4000], "small": [[10], 10], "wide": [[3], 3]}
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert big.dtype == np.float32 and np.array_equal(big, arrays["big"].numpy())
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "a" / "wide.npy"), arrays["wide"].numpy())
+    for where in ("b", "c"):
+        got = bench.dump_outputs(arrays, str(tmp_path / where), budget=1200)
+        assert got == {"big": [[4, 1000], 100], "small": [[10], 10], "wide": [[3], 3]}
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert b.shape == (100,) and np.array_equal(b, c)
+    flat = arrays["big"].numpy().reshape(-1)
+    keep = np.sort(np.random.default_rng(0).choice(flat.size, 100, replace=False))
+    assert np.array_equal(b, flat[keep])
+    assert sum(np.load(p).nbytes for p in (tmp_path / "b").glob("*.npy")) <= 1200
+    # write=False (the other ranks of a multi-GPU run): same bookkeeping, no files
+    assert bench.dump_outputs(arrays, str(tmp_path / "d"), write=False)["big"] == [[4, 1000], 4000]
+    assert not (tmp_path / "d").exists()
+
+
 PROBE = r'''
 import json, os, sys
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])

@@ -26,7 +26,7 @@ def test_bench_two_ranks_shared_gpu_gloo():
     too, and the cross-rank checks clean: the same global batches everywhere (es) and bit-identical
     replicas (dp, 2 model chunks of 4 models on 2048 rows -- the shape whose engines pick a split-K
     gradient on their own)."""
-    r = _bench("--gpus", "2", "--shared-gpu", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5",
+    r = _bench("--gpus", "2", "--shared-gpu", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5", "--full",
                "--no-eval", "--settle-ms", "0", "--ring-rows", "131072", "--parallelism", "es")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -45,6 +45,30 @@ def test_bench_two_ranks_shared_gpu_gloo():
     cal = rec["comm_calibration"]  # the node's own collective rates, timed before the mode was chosen
     assert cal["backend"] == "gloo" and cal["all_gather"]["bytes_per_rank"] == 2048 * 512 * 2
     assert cal["all_reduce"]["bus_GBps"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain one-GPU run times exactly ``--steps`` steps and evaluates nothing else (no FVU@L0 block:
+    that is ``--full``); ``--dump-outputs`` writes the last timed step's losses and the parameters as
+    float32 .npy files of at most 64 MB in all (the 2 x 33.5 MB weight stacks as seeded samples)."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = _bench("--gpus", "1", "--steps", "4", "--warmup", "2", "--settle-ms", "0", "--ring-rows", "131072",
+               "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 4 and rec["full"] is False and "fvu_at_l0" not in rec
+    assert sum(rec["graph_replays"]["timed"]) == 4
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] * rec["ms_per_step"] / 1e3 / 2048 - 1) < 1e-2
+    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(files) == set(rec["dumped_outputs"]) and {"losses", "encoder", "decoder", "encoder_bias"} <= set(files)
+    assert files["losses"].shape == (8, 6) and files["encoder_bias"].shape == (8, 2048)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 10 ** 6
+    assert rec["dumped_outputs"]["encoder"][0] == [8, 2048, 512] and files["encoder"].ndim == 1
 
 
 def test_bench_more_gpus_than_present_fails_fast():
