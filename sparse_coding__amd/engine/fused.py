@@ -773,6 +773,87 @@ class FusedSAEEnsemble:
         var = s2 - s1.pow(2).sum(-1) / N  # total sum of squares about the mean
         return (se / var).float(), (l0 / N).float()
 
+    def _resample_unsupported(self) -> Optional[str]:
+        if self.kind == "threshold":
+            return "threshold SAEs (learned scale / gain / centering) have no resampling rule"
+        if self.kind == "reverse":
+            return "reverse SAEs (bias-subtracted codes) have no resampling rule"
+        if self.learned_center:
+            return "learned centering: the pool rows would have to be re-centred per model"
+        if self.centering is not None:
+            return "affine centering: the pool rows would have to be re-centred per model"
+        return None
+
+    @torch.no_grad()
+    def resample_dead(self, rows: torch.Tensor, *, rule: str = "reference", pick: str = "worst", ratio: float = 0.2,
+                      use_window_counts: bool = True, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """Re-seed dead features from badly reconstructed rows of the candidate pool ``rows`` [N, d]
+        (N a positive multiple of the batch size); returns the per-model number of resampled features
+        as a device tensor [G].  Never synchronises.
+
+        The pool is scored forward-only (as ``evaluate``: the scratch buffers ``c`` / ``r`` / ``cmask`` /
+        ``enc_part`` are overwritten) with the encoder's exact fire counts and a per-row squared error
+        (``sc_row_sqerr``).  Feature (g, f) is dead when it never fires on the pool, exists
+        (f < dict_size[g], masked ensembles) and -- ``use_window_counts``, if the engine tracks counts and
+        has sampled rows since the last reset -- has ``feature_counts[g, f] == 0`` too (those counts are
+        SAMPLED every ``count_every`` steps: build the engine with ``count_every=1`` for exact ones).
+        ``engine.resample.plan_resample`` pairs dead features with pool rows (``pick``), ``rule`` sets
+        what is rewritten (``engine.resample.RULES``), and one ``sc_resample_rows`` launch edits masters,
+        Adam moments, bf16 shadows and row norms in place: captured step graphs stay valid.  Afterwards
+        ``feature_counts`` and ``rows_seen`` are reset."""
+        from ..ops import resample as rs_ops
+        from . import resample as rs
+
+        why = self._resample_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"resample_dead: {why}")
+        rs._check(rule, pick)
+        B, G, n, d = self.batch_size, self.n_models, self.n, self.d
+        if rows.dim() != 2 or rows.shape[1] != d:
+            raise ValueError(f"rows must be [N, {d}], got {tuple(rows.shape)}")
+        N = rows.shape[0]
+        if N <= 0 or N % B:
+            raise ValueError(f"the pool needs a positive multiple of the batch size ({B}) rows, got {N}")
+        dev = self.device
+        pool = self._x_bf16(rows)
+        bias = self.params[self._bkey]
+        cnt_part = self.cnt_part
+        if cnt_part is None:  # (an engine built without feature counting: the pool still needs them)
+            cnt_part = getattr(self, "_pool_cnt_part", None)
+            if cnt_part is None:
+                cnt_part = self._pool_cnt_part = torch.zeros(G, B // 128, n, device=dev)
+        err = torch.empty(G, N, device=dev)
+        fired = torch.zeros(G, n, device=dev)
+        for i in range(0, N, B):
+            x = pool[i:i + B]
+            gemm_ops.encode_relu(x, self.enc_shadow, bias, self.c, self.enc_part, cnt_part, self.nactive,
+                                 mask_out=self.cmask, act=self.act, live_host=self._live)
+            gemm_ops.decode_residual(self.c, self.dec_shadow, x, self.r, self.dec_part)
+            rs_ops.row_sqerr(self.r, err, i)
+            fired += cnt_part.sum(1)
+        dead = fired == 0
+        live = None
+        if self.nactive is not None:
+            live = torch.arange(n, device=dev).unsqueeze(0) < self.nactive.unsqueeze(1)
+            dead &= live
+        if use_window_counts and self.feature_counts is not None and self.rows_seen > 0:
+            dead &= self.feature_counts == 0
+        dead_idx, src_idx, cnt = rs.plan_resample(dead, err, pick=pick, generator=generator)
+        scale = rs.resample_scales(self.params["encoder"], dead, live, rule=rule, ratio=ratio)
+        untied = self.kind == "untied"
+        rs_ops.resample_rows(dead_idx, src_idx, cnt, pool, scale, self.params["encoder"], self.m["encoder"],
+                             self.v["encoder"], self.enc_shadow, bias, self.m[self._bkey], self.v[self._bkey],
+                             self.norms,
+                             dec=self.params["decoder"] if untied else None,
+                             dec_m=self.m["decoder"] if untied else None,
+                             dec_v=self.v["decoder"] if untied else None,
+                             dec_shadow=self.dec_shadow if untied else None, **rs.RULES[rule])
+        if self.feature_counts is not None:
+            self.feature_counts.zero_()
+        self.rows_seen = 0
+        self._bsq_dirty = True
+        return cnt
+
     def feature_frequency(self) -> torch.Tensor:
         """Per-feature firing frequency [G, n] = feature_counts / rows_seen.  The counts are SAMPLED:
         the encoder epilogue accumulates them only on counting steps (every ``count_every``-th step, or

@@ -276,6 +276,47 @@ class EnsembleTrainer:
         new, _, _ = self.fista(ens.params["decoder"], x, codes.float(), l1)
         ens.params["decoder"].data.copy_(new)
 
+    # ------------------------------------------------------------------ dead-feature resampling
+    def resample_dead(self, rows: torch.Tensor, **kw) -> List[int]:
+        """Re-seed dead features of every model from the candidate pool ``rows`` [N, d]
+        (``engine/resample.py``; keywords ``rule``, ``pick``, ``ratio``, ``generator`` and, on the fused
+        engine, ``use_window_counts``).  Returns the per-model counts (one host read).
+
+        The fused SAE engine runs ``FusedSAEEnsemble.resample_dead`` (N a multiple of its batch size;
+        under ensemble sharding each rank resamples its own models from the rows it is given, N a
+        multiple of the engine's global batch).  The analytic and eager engines with an untied / tied
+        SAE signature run the same rules in fp32 torch: dead means "never fires on ``rows``".  Data
+        parallel trainers and every other kind raise ``NotImplementedError``."""
+        from . import resample as rs
+
+        if self.dp is not None:
+            raise NotImplementedError("resample_dead: data-parallel replicas (parallel='dp'/'zero1') would need "
+                                      "a common candidate pool on every rank")
+        if self.kind == "fused-sae":
+            cnt = self.impl.resample_dead(rows.to(self.device), **kw)
+            return [int(c) for c in cnt.cpu()]
+        kind = analytic._KINDS.get(self.sig)
+        if self.kind not in ("analytic", "eager") or kind is None:
+            raise NotImplementedError(f"resample_dead: no resampling rule for the {self.kind} engine with "
+                                      f"{getattr(self.sig, '__name__', self.sig)}")
+        impl = self.impl
+        buffers = getattr(impl, "buffers", {})
+        if kind == "tied" and "center_rot" in buffers:
+            rot = buffers["center_rot"].float()
+            ident = (torch.equal(rot, torch.eye(rot.shape[-1], device=rot.device).expand_as(rot))
+                     and not bool(buffers["center_trans"].any()) and bool((buffers["center_scale"] == 1).all()))
+            if not ident:
+                raise NotImplementedError("resample_dead: affine centering -- the pool rows would have to be "
+                                          "re-centred per model")
+        kw.pop("use_window_counts", None)  # (these engines keep no fire counts: the pool decides)
+        if self.kind == "analytic":
+            m, v = impl.m, impl.v
+        else:
+            m, v = impl.optim_states.mu, impl.optim_states.nu
+        live = ~buffers["coef_mask"].bool() if "coef_mask" in buffers else None
+        cnt = rs.resample_stacked(impl.params, m, v, rows, kind, live=live, **kw)
+        return [int(c) for c in cnt.cpu()]
+
     # ------------------------------------------------------------------ export / state
     def hyperparams(self, ensemble_hyperparams: Sequence[str] = (), buffer_hyperparams: Sequence[str] = ("l1_alpha",),
                     local: bool = False) -> List[dict]:

@@ -52,6 +52,10 @@ def signatures():
                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
                          c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_int],
+        "sc_row_sqerr": [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p],
+        "sc_resample_rows": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_int, c_int, c_int,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,

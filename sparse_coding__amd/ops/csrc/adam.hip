@@ -76,28 +76,7 @@ __global__ __launch_bounds__(256) void shadow_rows_kernel(const float* p, uint16
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float* P = p + row * d;
-  float ss = 0.f;
-  for (int e = lane * 4; e < d; e += 256) {
-    const float4 v = *reinterpret_cast<const float4*>(P + e);
-    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  }
-  float sc = 1.f;
-  if (norm) {
-    ss = wave_sum(ss);
-    const float nrm = fmaxf(sqrtf(ss), 1e-8f);
-    sc = 1.f / nrm;
-    if (norms && lane == 0) norms[row] = nrm;
-  }
-  for (int e = lane * 4; e < d; e += 256) {
-    const float4 v = *reinterpret_cast<const float4*>(P + e);
-    ushort4 h;
-    h.x = f2bf(v.x * sc);
-    h.y = f2bf(v.y * sc);
-    h.z = f2bf(v.z * sc);
-    h.w = f2bf(v.w * sc);
-    *reinterpret_cast<ushort4*>(shadow + row * d + e) = h;
-  }
+  shadow_row(p + row * d, shadow + row * d, norms ? norms + row : nullptr, d, norm, lane);
 }
 
 struct BiasArgs {

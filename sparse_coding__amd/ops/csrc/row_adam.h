@@ -15,6 +15,33 @@ __device__ __forceinline__ void bias_corrections(float b1, float b2, int t, floa
   bc2 = 1.f - __powf(b2, (float)t);
 }
 
+// One row of a bf16 shadow from its fp32 master, one wave: P -> S (row-normalised if norm, the row
+// norm to *nrm_out).  The per-row body of shadow_rows_kernel (adam.hip), shared with the resampling
+// kernel (resample.hip) so that both reduce the norm in one order and write the same bits.
+__device__ __forceinline__ void shadow_row(const float* P, uint16_t* S, float* nrm_out, int d, int norm, int lane) {
+  float ss = 0.f;
+  for (int e = lane * 4; e < d; e += 256) {
+    const float4 v = *reinterpret_cast<const float4*>(P + e);
+    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+  }
+  float sc = 1.f;
+  if (norm) {
+    ss = wave_sum(ss);
+    const float nrm = fmaxf(sqrtf(ss), 1e-8f);
+    sc = 1.f / nrm;
+    if (nrm_out && lane == 0) *nrm_out = nrm;
+  }
+  for (int e = lane * 4; e < d; e += 256) {
+    const float4 v = *reinterpret_cast<const float4*>(P + e);
+    ushort4 h;
+    h.x = f2bf(v.x * sc);
+    h.y = f2bf(v.y * sc);
+    h.z = f2bf(v.z * sc);
+    h.w = f2bf(v.w * sc);
+    *reinterpret_cast<ushort4*>(S + e) = h;
+  }
+}
+
 // One dictionary row of the fused Adam, one wave (d = 256 NV): applies the norm Jacobian (norm rows),
 // the Adam update, recomputes the row norm and writes the bf16 shadow (normalised for norm rows).
 // GBF: the gradient arrives in bf16 (the weight-gradient GEMM's bf16 epilogue): 1/7 of the HBM bytes

@@ -24,6 +24,7 @@ from __future__ import annotations
 import datetime
 import os
 import time
+import warnings
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -143,6 +144,33 @@ def _load_chunk_into_ring(folder: ChunkFolder, handle, ring: DeviceRing, means: 
     return dev.shape[0]
 
 
+def _resample_trainer(trainer: EnsembleTrainer, ring: DeviceRing, cfg, chunk: int, logger: Optional[Logger],
+                      global_step: int) -> bool:
+    """Dead-feature resampling of one trainer from the chunk it just trained on (reference
+    huge_batch_size.py:204-250): a seeded draw of ``resample_pool_batches`` batches of ring rows, in the
+    ring's own dtype, is the candidate pool; the per-model counts are logged as
+    ``{ensemble}_{hparams}_n_resampled``.  Returns False (after one warning) when the trainer's engine
+    has no resampling rule."""
+    B = trainer.batch_size
+    nrows = min(max(1, int(getattr(cfg, "resample_pool_batches", 8))) * B, ring.size - ring.size % B)
+    if nrows <= 0:
+        warnings.warn(f"resampling skipped for {trainer.name}: the ring holds fewer than {B} rows")
+        return True
+    gen = torch.Generator(device=ring.device)  # (its own stream: the ring's batch order is untouched)
+    gen.manual_seed(int(cfg.seed) + 1000003 * (chunk + 1))
+    idx = torch.randperm(ring.size, device=ring.device, generator=gen)[:nrows]
+    try:
+        counts = trainer.resample_dead(ring.view().index_select(0, idx), rule=getattr(cfg, "resample_rule", "reference"),
+                                       pick=getattr(cfg, "resample_pick", "worst"), generator=gen)
+    except NotImplementedError as e:
+        warnings.warn(f"resampling skipped for {trainer.name}: {e}")
+        return False
+    if logger is not None:
+        hp = trainer.hyperparams(cfg.ensemble_hyperparams, cfg.buffer_hyperparams, local=True)
+        logger.log(model_metric_names(trainer.name, hp, [{"n_resampled": c} for c in counts]), global_step)
+    return True
+
+
 def sweep(ensemble_init_func, cfg, info: Optional[DistInfo] = None) -> List[Tuple[Any, dict]]:
     """Run a hyper-parameter sweep over the chunks in ``cfg.dataset_folder`` (reference big_sweep.py:341-429)."""
     info = info or init_distributed()
@@ -206,6 +234,8 @@ def sweep(ensemble_init_func, cfg, info: Optional[DistInfo] = None) -> List[Tupl
                       seed=cfg.seed + info.rank)
     handle = folder.prefetch(int(chunk_order[start])) if start < len(chunk_order) else None
     learned_dicts: List[Tuple[Any, dict]] = []
+    resample_every = int(getattr(cfg, "resample_every", 0) or 0)
+    no_resample = set()  # trainers whose engine has no resampling rule (warned once, then skipped)
     for i in range(start, len(chunk_order)):
         chunk_idx = int(chunk_order[i])
         t0 = time.time()
@@ -222,6 +252,9 @@ def sweep(ensemble_init_func, cfg, info: Optional[DistInfo] = None) -> List[Tupl
                 continue
             global_step = ensemble_train_loop(t, ring, t.batch_size, None, logger, cfg.log_every,
                                               cfg.ensemble_hyperparams, cfg.buffer_hyperparams, global_step)
+            if resample_every and (i + 1) % resample_every == 0 and id(t) not in no_resample:
+                if not _resample_trainer(t, ring, cfg, i, logger, global_step):
+                    no_resample.add(id(t))
         if device.type == "cuda":
             torch.cuda.synchronize(device)
         learned_dicts = []

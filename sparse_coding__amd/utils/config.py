@@ -162,6 +162,11 @@ class TrainArgs(BaseArgs):
     log_every: int = 100
     log_dir: str = ""
     resume: bool = True
+    # dead-feature resampling in the sweep driver (engine/resample.py); 0 = off
+    resample_every: int = 0         # in chunks
+    resample_rule: str = "reference"  # reference | anthropic
+    resample_pick: str = "worst"      # worst | loss_sq
+    resample_pool_batches: int = 8
 
 
 @dataclass
