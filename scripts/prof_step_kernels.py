@@ -27,7 +27,7 @@ for _ in range(5):
     gemm.decode_residual(e.c, e.dec_shadow, x, e.r, e.dec_part)
     gemm.code_grad(e.r, e.dec_shadow, e.c, e.l1, e.dpre, e.colpart, mask=e.cmask)
     gemm.weight_grads([[(e.c, e.r)], [(e.dpre, x)]], [e.g_dec, e.g_enc], 1e-6)
-    e._apply_update_kernels()  # the fused step tail (row Adam + losses + bias Adam)
+    e.update()  # the fused step tail (row Adam + losses + bias Adam)
 torch.cuda.synchronize()
 # config 4 top-k: bf16 scores GEMM + select (8 models, B=2048, d=768, n=6144)
 xt = (torch.randn(2048, 768, device=dev) * 0.3).to(torch.bfloat16)

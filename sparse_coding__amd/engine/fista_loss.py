@@ -183,8 +183,7 @@ class FusedFistaLossEnsemble:
 
     def apply_update(self):
         e = self.engine
-        e.adam_rows_all()
-        e._bias_loss(update=True, reduced=True)
+        e.update(reduced=True, fused=False)
         e._host_step()
 
     def step_batch(self, batch):

@@ -1,6 +1,6 @@
 """``FusedSAEEnsemble``: the MI355X training engine for SAE ensembles.
 
-One training step for ALL models of an ensemble is six kernel launches (the
+One training step for ALL models of an ensemble is five kernel launches (the
 reference runs ``vmap(grad(loss))`` + ``vmap(adam.update)``,
 ``autoencoders/ensemble.py:175-193``, i.e. dozens of eager ops):
 
@@ -8,8 +8,15 @@ reference runs ``vmap(grad(loss))`` + ``vmap(adam.update)``,
 2. ``decode_residual`` R = c W_hat - x                (MFMA, sum R^2 epilogue)
 3. ``code_grad``       dpre = 1[c>0](R W_hat^T + l d/2) (MFMA, bias-grad column partials)
 4. ``weight_grads``    dW_hat = c^T R, dW_e = dpre^T x (two problems, one launch)
-5. ``adam_rows``       norm-Jacobian + Adam + bf16 shadow for decoder and encoder
-6. ``bias_loss``       reduce partials -> losses, Adam on the bias
+5. ``step_tail``       norm-Jacobian + Adam + bf16 shadow for decoder and encoder; reduce
+                       partials -> losses; Adam on the bias; the NEXT step's batch gather;
+                       the device step counter advanced by the last block
+
+``FusedSAEEnsemble.update`` is the one place that knows the order of step 5.  Engines the
+fused tail does not cover (threshold / reverse / learned-centre kinds, d > 1024, or
+``fused_tail=False``) and the host-issued data-parallel paths run it as separate launches
+instead: the small extra Adam of threshold / centred kinds, ``adam_rows``, then ``bias_loss``
+(loss terms, then bias Adam).
 
 State layout (per device): fp32 masters ``[G, n, d]``; Adam moments; bf16
 shadows the GEMMs read (decoder shadow already row-normalised, so no kernel
@@ -26,8 +33,6 @@ same kernels with the ENC_ACT / DC_ACT epilogues.  Masked models pass per-model
 """
 
 from __future__ import annotations
-
-import os
 
 from typing import Dict, List, Optional, Sequence
 
@@ -59,7 +64,8 @@ class FusedSAEEnsemble:
 
     def __init__(self, models, sig, lr=1e-3, batch_size=256, device="cuda", betas=(0.9, 0.999),
                  eps=1e-8, track_feature_counts=True, kind: Optional[str] = None,
-                 count_every: int = 8, wgrad_split="auto", grad_dtype: Optional[str] = None):
+                 count_every: int = 8, wgrad_split="auto", grad_dtype: Optional[str] = None,
+                 fused_tail: bool = True):
         self.sig = sig
         self.kind = kind or getattr(sig, "fused_kind", None)
         # FunctionalTiedCenteredSAE (sae_ensemble.py:162-228): the tied kernels on x - center
@@ -227,10 +233,10 @@ class FusedSAEEnsemble:
         self.out = torch.zeros(G, 6, device=dev)
         # fused step tail (csrc/adam.hip step_tail_kernel: row Adam + loss terms + bias Adam + the next
         # step's batch gather in ONE launch) for the plain untied / tied single-device step; it keeps
-        # per-32-column b^2 partial sums (parity-double-buffered by the step counter) for |b|
-        self._tail_ok = (self.kind in ("untied", "tied") and self.act == gemm_ops.ACT_RELU and not self.learned_center
-                         and n % 32 == 0 and d <= 1024
-                         and os.environ.get("SC_FUSED_TAIL", "1") not in ("", "0"))
+        # per-32-column b^2 partial sums (parity-double-buffered by the step counter) for |b|.
+        # ``fused_tail=False`` keeps the separate kernels (A/B runs, the tail's reference in the tests)
+        self._tail_ok = (bool(fused_tail) and self.kind in ("untied", "tied") and self.act == gemm_ops.ACT_RELU
+                         and not self.learned_center and n % 32 == 0 and d <= 1024)
         self._bsq = torch.zeros(2, G, n // 32, device=dev) if self._tail_ok else None
         self._ticket = torch.zeros(adam_ops.TICKET_INTS, device=dev, dtype=torch.int32) if self._tail_ok else None
         self._bsq_dirty = True
@@ -436,43 +442,75 @@ class FusedSAEEnsemble:
         adam_ops.adam_rows(self._adam_sets()[:1], self.lr, self.step_count + 1, *self.betas, self.eps,
                            step_dev=self.step_dev, live=self.nactive)
 
-    def adam_rows_all(self):
-        """Row Adam on every dictionary set (data-parallel update after the reduction)."""
-        adam_ops.adam_rows(self._adam_sets(), self.lr, self.step_count + 1, *self.betas, self.eps,
-                           step_dev=self.step_dev, live=self.nactive)
-
     def adam_second(self, reduced_bias=True):
         """Encoder Adam (untied) and bias Adam + loss reduction (advances the step counter)."""
         if self.kind == "untied":
             adam_ops.adam_rows(self._adam_sets()[1:], self.lr, self.step_count + 1, *self.betas, self.eps,
                                step_dev=self.step_dev, live=self.nactive)
-        self._bias_loss(update=True, reduced=reduced_bias)
+        self._bias_loss(reduced=reduced_bias)
         self._host_step()
 
     def apply_update(self):
-        """Kernels 5-6: fused Adam on the weights, then bias Adam + loss reduction."""
+        """The update of the single-device step (``update``) and the host step bookkeeping."""
         self._tail_ready()
-        self._apply_update_kernels()
+        self.update()
         self._host_step()
 
-    def _apply_update_kernels(self, gather=None):
-        if self._tail_ok:
-            # one launch: row Adam + loss terms + bias Adam (+ the next step's batch gather), the
-            # device step counter advanced by its last block
-            adam_ops.step_tail(self._adam_sets(), self.lr, *self.betas, self.eps, self.step_dev,
-                               self.params[self._bkey], self.m[self._bkey], self.v[self._bkey], self.colpart,
+    def row_sets(self, lo: int, hi: int, grads):
+        """The row-Adam parameter sets of rows [lo, hi) of the flattened [G n, d] dictionary stacks (a
+        ZeRO-1 shard) for ``update``; ``grads``: the shard's [hi - lo, d] fp32 gradients, the decoder's
+        first (untied), as ``_adam_sets`` orders them."""
+        d = self.d
+        rows = lambda t: t.view(-1, d)[lo:hi]  # noqa: E731
+        grads = [g.view(hi - lo, d) for g in grads]
+        norms = self.norms.view(-1)[lo:hi]
+        enc = dict(p=rows(self.params["encoder"]), m=rows(self.m["encoder"]), v=rows(self.v["encoder"]),
+                   shadow=rows(self.enc_shadow))
+        if self.kind == "untied":
+            return [dict(p=rows(self.params["decoder"]), g=grads[0], m=rows(self.m["decoder"]),
+                         v=rows(self.v["decoder"]), shadow=rows(self.dec_shadow), norms=norms, norm=True),
+                    dict(enc, g=grads[1], norms=None, norm=False)]
+        return [dict(enc, g=grads[0], norms=norms, norm=True)]
+
+    def update(self, sets=None, *, reduced: bool = False, row0: Optional[int] = None, gather=None,
+               fused: Optional[bool] = None):
+        """The end of a step, and the one place that knows its order: the extra Adam of threshold /
+        learned-centre kinds (their gradients read the dictionary and must see it BEFORE this step's
+        update: every gradient from the same parameters, vmap(grad), autoencoders/ensemble.py:119-123),
+        then row Adam on ``sets``, the loss terms and bias Adam -- as the ONE launch of the fused step
+        tail (``fused``; default: whenever the engine supports it), which also fetches the next step's
+        batch (``gather``, see ``adam_ops.step_tail``), or as the separate ``adam_rows`` and
+        ``bias_loss`` launches.  Either way the device step counter advances at the end.
+
+        ``sets``: the row-Adam parameter sets (default: the whole stacks with this step's gradients,
+        ``_adam_sets``), or ``row_sets(lo, hi, grads)`` with ``row0=lo`` for a row shard.  ``reduced``:
+        the bias gradient (and a threshold / centred kind's extra sums) was already summed, scaled and
+        possibly all-reduced into ``g_bias`` (data parallel), instead of this rank's column partials."""
+        fused = self._tail_ok if fused is None else bool(fused)
+        if fused and not self._tail_ok:
+            raise ValueError(f"this engine (kind {self.kind}, d = {self.d}) has no fused step tail")
+        if gather is not None and not fused:
+            raise ValueError("only the fused step tail fetches the next batch (gather)")
+        if self.kind == "threshold" or self.learned_center:
+            self._threshold_extra_adam(reduced=reduced)
+        kw = dict(live=self.nactive)
+        if sets is None:
+            sets = self._adam_sets()
+            kw.update(self._adam_split_kw())
+        if fused:
+            colpart, gscale = (self.g_bias, 1.0) if reduced else (self.colpart, self._alpha)
+            # (only the single-device step launches its row blocks compacted to a masked ensemble's live rows)
+            adam_ops.step_tail(sets, self.lr, *self.betas, self.eps, self.step_dev,
+                               self.params[self._bkey], self.m[self._bkey], self.v[self._bkey], colpart,
                                self.enc_part, self.dec_part, self.l1, self.bias_decay, self.out, self.batch_size,
-                               self._alpha, self._bsq, self._ticket,
+                               gscale, self._bsq, self._ticket,
                                cnt_part=self.cnt_part if self._counted else None,
                                feat_count=self.feature_counts if self._counted else None, gather=gather,
-                               live=self.nactive, live_host=self._live, **self._adam_split_kw())
+                               row0=row0, live_host=None if reduced else self._live, **kw)
             return
-        # scale / centering first: their gradients read the pre-update dictionary (adam_first)
-        if self.kind == "threshold" or self.learned_center:
-            self._threshold_extra_adam()
-        adam_ops.adam_rows(self._adam_sets(), self.lr, self.step_count + 1, *self.betas, self.eps,
-                           step_dev=self.step_dev, live=self.nactive, **self._adam_split_kw())
-        self._bias_loss(update=True, reduced=False)
+        adam_ops.adam_rows(sets, self.lr, self.step_count + 1, *self.betas, self.eps, rows_per_model=self.n,
+                           step_dev=self.step_dev, row0=row0 or 0, **kw)
+        self._bias_loss(reduced=reduced)  # (marks the tail's b^2 partials stale)
 
     def _threshold_extra_adam(self, reduced: bool = False):
         """Scale and centering of the threshold SAE (small vectors; before the bias / loss
@@ -531,10 +569,9 @@ class FusedSAEEnsemble:
             self.rows_seen += self.batch_size
         self.step_count += 1
 
-    def _bias_loss(self, update, reduced, defer_step=False):
-        G, B, n, d = self.n_models, self.batch_size, self.n, self.d
-        if update:
-            self._bsq_dirty = True  # (a bias update outside the fused tail)
+    def _bias_loss(self, reduced):
+        B, d = self.batch_size, self.d
+        self._bsq_dirty = True  # (a bias update outside the fused tail)
         b1, b2 = self.betas
         if reduced:  # bias gradient already summed (and possibly all-reduced) into g_bias
             colpart, tm, gscale = self.g_bias, 1, 1.0
@@ -546,8 +583,7 @@ class FusedSAEEnsemble:
                            self.step_count + 1, gscale=gscale,
                            cnt_part=self.cnt_part if self._counted else None,
                            feat_count=self.feature_counts if self._counted else None,
-                           b1=b1, b2=b2, eps=self.eps, update=update,
-                           step_dev=self.step_dev, defer_step=defer_step)
+                           b1=b1, b2=b2, eps=self.eps, step_dev=self.step_dev)
 
     def step_batch(self, batch, expand_dims=True):
         """One Adam step of every model on ``batch [B, d]``; returns a device tensor [G, 6]:
@@ -586,7 +622,7 @@ class FusedSAEEnsemble:
         self.backward_weights(x)
         if before_update is not None:  # e.g. a stream wait the update (its next-batch fetch) needs
             before_update()
-        self._apply_update_kernels(gather if self._tail_ok else None)
+        self.update(gather=gather if self._tail_ok else None)
 
     def add_static_input(self, t: torch.Tensor) -> int:
         """Register another persistent input buffer [B, d] bf16: ``step_batch(t)`` then replays
@@ -741,6 +777,16 @@ class FusedSAEEnsemble:
         self._host_step()
         return self.out
 
+    def _forward_only(self, x, target=None, cnt_part=None):
+        """Codes and residual of one prepared batch ``x`` without gradients (``evaluate`` and the pool
+        scoring of ``resample_dead``): overwrites the scratch buffers ``c`` / ``r`` / ``cmask`` and the
+        epilogue partials ``enc_part`` / ``dec_part``; fire counts go to ``cnt_part`` when given.
+        ``target``: the rows to reconstruct when they are not ``x`` (threshold SAEs)."""
+        gemm_ops.encode_relu(x, self.enc_shadow, self.params[self._bkey], self.c, self.enc_part, cnt_part,
+                             self.nactive, mask_out=self.cmask, act=self.act,
+                             ascale=self.s2 if self.kind == "threshold" else None, live_host=self._live)
+        gemm_ops.decode_residual(self.c, self.dec_shadow, x if target is None else target, self.r, self.dec_part)
+
     @torch.no_grad()
     def evaluate(self, rows: torch.Tensor):
         """FVU and mean L0 of every model on ``rows`` [N, d] (N a multiple of the batch size),
@@ -758,13 +804,9 @@ class FusedSAEEnsemble:
         s2 = torch.zeros(G, device=self.device, dtype=torch.float64)
         for i in range(0, N, B):
             xin = self._x_bf16(rows[i:i + B])
-            x = self.prepare(xin)
-            gemm_ops.encode_relu(x, self.enc_shadow, self.params[self._bkey], self.c, self.enc_part, None,
-                                 self.nactive, mask_out=self.cmask, act=self.act,
-                                 ascale=self.s2 if self.kind == "threshold" else None, live_host=self._live)
-            if self.kind == "threshold":  # reconstructs the uncentred rows
-                x = xin
-            gemm_ops.decode_residual(self.c, self.dec_shadow, x, self.r, self.dec_part)
+            xp = self.prepare(xin)
+            x = xin if self.kind == "threshold" else xp  # (threshold SAEs reconstruct the uncentred rows)
+            self._forward_only(xp, target=x)
             se += self.dec_part.sum(1).double()
             l0 += self.enc_part[..., 1].sum(1).double()
             xf = x.double() if x.dim() == 3 else x.double().expand(G, B, self.d)
@@ -826,9 +868,7 @@ class FusedSAEEnsemble:
         fired = torch.zeros(G, n, device=dev)
         for i in range(0, N, B):
             x = pool[i:i + B]
-            gemm_ops.encode_relu(x, self.enc_shadow, bias, self.c, self.enc_part, cnt_part, self.nactive,
-                                 mask_out=self.cmask, act=self.act, live_host=self._live)
-            gemm_ops.decode_residual(self.c, self.dec_shadow, x, self.r, self.dec_part)
+            self._forward_only(x, cnt_part=cnt_part)
             rs_ops.row_sqerr(self.r, err, i)
             fired += cnt_part.sum(1)
         dead = fired == 0

@@ -55,7 +55,8 @@ def auto_sparse_k(B: int, n: int, d: int, margin: float = 1.3) -> int:
 
 class FusedTopKEnsemble:
     def __init__(self, models, sig=None, lr=1e-3, batch_size=256, device="cuda", betas=(0.9, 0.999), eps=1e-8,
-                 grad_dtype: str = "bf16", sparse_k: Union[int, str] = "auto", scores_dtype: Optional[str] = None):
+                 grad_dtype: str = "bf16", sparse_k: Union[int, str] = "auto", scores_dtype: Optional[str] = None,
+                 fused_tail: bool = True):
         from ..models.topk import TopKEncoder
 
         self.sig = sig or TopKEncoder
@@ -120,8 +121,8 @@ class FusedTopKEnsemble:
             raise ValueError(f"grad_dtype must be 'fp32' or 'bf16', got {grad_dtype!r}")
         self.g = torch.empty(G, n, d, device=dev, dtype=bf if grad_dtype == "bf16" else torch.float32)
         self.mse = torch.zeros(G, device=dev)
-        # fused tail (SC_TOPK_TAIL=0: Adam + torch reductions + counter increment as separate launches)
-        self._tail = os.environ.get("SC_TOPK_TAIL", "1") not in ("", "0") and d <= 1024
+        # fused tail (``fused_tail=False``: Adam + torch reductions + counter increment as separate launches)
+        self._tail = bool(fused_tail) and d <= 1024
         self._ticket = torch.zeros(adam_ops.TICKET_INTS, device=dev, dtype=torch.int32)
         self.x_static = torch.zeros(B, d, device=dev, dtype=bf)
         self.use_graph = False

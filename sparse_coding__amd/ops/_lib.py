@@ -51,7 +51,7 @@ def signatures():
         "sc_bias_loss": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
-                         c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_int],
+                         c_float, c_float, c_void_p, c_void_p, c_int],
         "sc_row_sqerr": [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p],
         "sc_resample_rows": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_int, c_int, c_int,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

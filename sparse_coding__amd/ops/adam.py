@@ -13,6 +13,35 @@ def _vp(seq):
     return (C.c_void_p * len(seq))(*[_lib.ptr(t) for t in seq])
 
 
+def _check_sets(sets, name):
+    """Every p / g / m / v of the parameter sets is contiguous, of the first set's shape, and fp32 (the
+    gradients may all be bf16 instead); returns whether the gradients are bf16."""
+    shp = tuple(sets[0]["p"].shape)
+    gbf16 = sets[0]["g"].dtype == torch.bfloat16
+    for s in sets:
+        for k in ("p", "g", "m", "v"):
+            t = s[k]
+            want = torch.bfloat16 if (k == "g" and gbf16) else torch.float32
+            if t.dtype != want or tuple(t.shape) != shp or not t.is_contiguous():
+                raise ValueError(f"{name} set tensor {k} must be contiguous {want} {shp} (bf16 gradients: all sets)")
+    return gbf16
+
+
+def _gather_args(gather):
+    """The C arguments (gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes; pointers as ints) of a step
+    tail's next-batch fetch ``gather`` = (ring buffer [N, d], perm int64, ep0 int32 [1], out [rows, d]),
+    or of none."""
+    if gather is None:
+        return (0,) * 8
+    gbuf, perm, ep0, gout = gather
+    row_bytes = gbuf.shape[-1] * gbuf.element_size()
+    if (row_bytes % 16 or gout.dtype != gbuf.dtype or gout.shape[-1] != gbuf.shape[-1] or not gout.is_contiguous()
+            or perm.dtype != torch.int64 or ep0.dtype != torch.int32):
+        raise ValueError("gather: contiguous rows of 16-byte multiples, int64 perm, int32 ep0")
+    return (_lib.ptr(gbuf), gbuf.shape[0], _lib.ptr(perm), perm.numel(), _lib.ptr(ep0), _lib.ptr(gout),
+            gout.shape[0], row_bytes)
+
+
 def adam_rows(sets, lr, step, b1=0.9, b2=0.999, eps=1e-8, rows_per_model=None, step_dev=None, nsplit=1,
               gstride=0, row0=0, live=None):
     """Fused row-wise Adam over one or two parameter sets.
@@ -35,14 +64,9 @@ def adam_rows(sets, lr, step, b1=0.9, b2=0.999, eps=1e-8, rows_per_model=None, s
     d = shp[-1]
     nrows = sets[0]["p"].numel() // d
     n = shp[1] if len(shp) == 3 else None
-    gbf16 = sets[0]["g"].dtype == torch.bfloat16
+    gbf16 = _check_sets(sets, "adam")
     gsize = 2 if gbf16 else 4
     for s in sets:
-        for k in ("p", "g", "m", "v"):
-            t = s[k]
-            want = torch.bfloat16 if (k == "g" and gbf16) else torch.float32
-            if t.dtype != want or tuple(t.shape) != tuple(sets[0]["p"].shape) or not t.is_contiguous():
-                raise ValueError(f"adam set tensor {k} must be contiguous {want} {shp} (bf16 gradients: all sets)")
         if s.get("shadow") is not None and (s["shadow"].dtype != torch.bfloat16 or s["shadow"].numel() != nrows * d):
             raise ValueError("shadow must be bf16 of the parameter's size")
         if s.get("norms") is not None and s["norms"].numel() != nrows:
@@ -81,11 +105,10 @@ def shadow_rows(p, shadow, norms=None, normalize=True):
 
 def bias_loss(b, m, v, colpart, tm, enc_part, enc_tiles, dec_part, dec_tiles, l1, bias_decay, lr,
               out, B, d, step, gscale, cnt_part=None, feat_count=None, b1=0.9, b2=0.999, eps=1e-8,
-              update=True, step_dev=None, defer_step=False):
+              step_dev=None):
     """Loss bookkeeping + bias Adam.  ``colpart`` [G, tm, n] holds partial sums of the bias
-    gradient; ``gscale`` converts their sum to dL/db.  ``defer_step``: leave the device step
-    counter alone (bias Adam uses ``*step_dev + 1``; the caller advances it) -- for running
-    concurrently with a row-Adam that reads the same counter."""
+    gradient; ``gscale`` converts their sum to dL/db.  ``step_dev``: the device step counter,
+    advanced here (bias Adam then takes its bias corrections from it instead of ``step``)."""
     G, n = b.shape
     bc1 = 1.0 - b1 ** max(step, 1)
     bc2 = 1.0 - b2 ** max(step, 1)
@@ -93,7 +116,7 @@ def bias_loss(b, m, v, colpart, tm, enc_part, enc_tiles, dec_part, dec_tiles, l1
         G, _lib.ptr(b), _lib.ptr(m), _lib.ptr(v), _lib.ptr(colpart), tm, _lib.ptr(enc_part),
         enc_tiles, _lib.ptr(dec_part), dec_tiles, _lib.ptr(cnt_part), _lib.ptr(feat_count),
         _lib.ptr(l1), _lib.ptr(bias_decay), _lib.ptr(lr), _lib.ptr(out), n, B, d, float(gscale), b1, b2, eps,
-        bc1, bc2, int(update), _lib.ptr(step_dev), _lib.stream_handle(), int(bool(defer_step)),
+        bc1, bc2, _lib.ptr(step_dev), _lib.stream_handle(),
         int(cnt_part.shape[1]) if cnt_part is not None and cnt_part.dim() == 3 else 0,
     )
     _lib.check(rc, "sc_bias_loss")
@@ -126,13 +149,7 @@ def step_tail(sets, lr, b1, b2, eps, step_dev, bias, bias_m, bias_v, colpart, en
         if len(shp) != 2 or row0 < 0 or row0 + shp[0] > G * n:
             raise ValueError(f"row shard [{shp}] at row {row0} is outside the [{G} x {n}] stack")
         shp = (G, n, d)
-    gbf16 = sets[0]["g"].dtype == torch.bfloat16
-    for s in sets:
-        for k in ("p", "g", "m", "v"):
-            t = s[k]
-            want = torch.bfloat16 if (k == "g" and gbf16) else torch.float32
-            if t.dtype != want or tuple(t.shape) != tuple(sets[0]["p"].shape) or not t.is_contiguous():
-                raise ValueError(f"step_tail set tensor {k} must be contiguous {want} {shp}")
+    gbf16 = _check_sets(sets, "step_tail")
     if len(shp) != 3 or shp[0] != G or shp[1] != n or n % 32 or d % 256 or d > 1024:
         raise ValueError(f"step_tail needs [G, n, d] sets with n % 32 == 0, d in 256..1024 (got {shp}, bias {G}x{n})")
     if tuple(bsq.shape) != (2, G, n // 32) or bsq.dtype != torch.float32 or not bsq.is_contiguous():
@@ -143,15 +160,7 @@ def step_tail(sets, lr, b1, b2, eps, step_dev, bias, bias_m, bias_v, colpart, en
     cnt_tm = cnt_part.shape[1] if cnt_part is not None else tm
     if tuple(colpart.shape) != (G, tm, n) or (cnt_part is not None and tuple(cnt_part.shape) != (G, cnt_tm, n)):
         raise ValueError("colpart must be [G, tm, n] and cnt_part [G, cnt_tm, n]")
-    gbuf = perm = ep0 = gout = None
-    grows = row_bytes = nbuf = nperm = 0
-    if gather is not None:
-        gbuf, perm, ep0, gout = gather
-        row_bytes = gbuf.shape[-1] * gbuf.element_size()
-        if (row_bytes % 16 or gout.dtype != gbuf.dtype or gout.shape[-1] != gbuf.shape[-1] or not gout.is_contiguous()
-                or perm.dtype != torch.int64 or ep0.dtype != torch.int32):
-            raise ValueError("gather: contiguous rows of 16-byte multiples, int64 perm, int32 ep0")
-        grows, nbuf, nperm = gout.shape[0], gbuf.shape[0], perm.numel()
+    gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes = _gather_args(gather)
     rows = (C.c_int * len(sets))(*[nrows for _ in sets])
     norm = (C.c_int * len(sets))(*[int(bool(s["norm"])) for s in sets])
     rc = _lib.lib().sc_step_tail(
@@ -162,7 +171,7 @@ def step_tail(sets, lr, b1, b2, eps, step_dev, bias, bias_m, bias_v, colpart, en
         G, _lib.ptr(bias), _lib.ptr(bias_m), _lib.ptr(bias_v), _lib.ptr(colpart), tm, _lib.ptr(enc_part),
         enc_part.shape[1], _lib.ptr(dec_part), dec_part.shape[1], _lib.ptr(cnt_part), _lib.ptr(feat_count),
         _lib.ptr(l1), _lib.ptr(bias_decay), _lib.ptr(out), n, B, float(gscale), _lib.ptr(bsq), _lib.ptr(ticket),
-        _lib.ptr(gbuf), nbuf, _lib.ptr(perm), nperm, _lib.ptr(ep0), _lib.ptr(gout), grows, row_bytes,
+        gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes,
         int(nsplit), int(gstride), _lib.ptr(live), int(cnt_tm), int(row0 or 0),
         C.cast((C.c_int * len(live_host))(*[int(v) for v in live_host]), C.c_void_p)
         if (live_host is not None and live is not None) else None, _lib.stream_handle(),
@@ -191,20 +200,12 @@ def topk_tail(p, g, m, v, shadow, norms, lr, b1, b2, eps, step_dev, row_se, mse,
         raise ValueError("row_se must be contiguous fp32 [G, rows] and mse fp32 [G]")
     if ticket.dtype != torch.int32 or ticket.numel() < TICKET_INTS or step_dev is None:
         raise ValueError("ticket must be int32 and step_dev a device counter")
-    gbuf = perm = ep0 = gout = None
-    grows = row_bytes = nbuf = nperm = 0
-    if gather is not None:
-        gbuf, perm, ep0, gout = gather
-        row_bytes = gbuf.shape[-1] * gbuf.element_size()
-        if (row_bytes % 16 or gout.dtype != gbuf.dtype or gout.shape[-1] != gbuf.shape[-1] or not gout.is_contiguous()
-                or perm.dtype != torch.int64 or ep0.dtype != torch.int32):
-            raise ValueError("gather: contiguous rows of 16-byte multiples, int64 perm, int32 ep0")
-        grows, nbuf, nperm = gout.shape[0], gbuf.shape[0], perm.numel()
+    gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes = _gather_args(gather)
     rc = _lib.lib().sc_topk_tail(
         _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), _lib.ptr(shadow), _lib.ptr(norms), G, n, d,
         _lib.ptr(lr), b1, b2, eps, _lib.ptr(step_dev), int(gbf16), _lib.ptr(row_se), row_se.shape[1],
-        float(se_scale), _lib.ptr(mse), _lib.ptr(ticket), _lib.ptr(gbuf), nbuf, _lib.ptr(perm), nperm,
-        _lib.ptr(ep0), _lib.ptr(gout), grows, row_bytes, _lib.stream_handle(),
+        float(se_scale), _lib.ptr(mse), _lib.ptr(ticket), gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes,
+        _lib.stream_handle(),
     )
     _lib.check(rc, "sc_topk_tail")
 

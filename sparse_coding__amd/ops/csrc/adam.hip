@@ -98,34 +98,16 @@ struct BiasArgs {
   int nmodels;                     // G (the fused step tail indexes its b^2 partials by model)
   float gscale;                    // converts colpart sums to dL/db (2/(B d) for raw dpre_s)
   float b1, b2, eps, bc1, bc2;
-  int update;                      // 0: only losses (eval)
   int* step;                       // optional device step counter, advanced by loss_reduce
-  int defer_step;                  // 1: do not advance (the caller does, after a concurrent
-                                   //    row-Adam that reads the same counter); bias Adam uses *step + 1
 };
 
-// Phase 1 (one block per model): reduce the GEMM-epilogue partials to the
-// reference's loss terms and record |b| (pre-update) for the bias-decay term.
-__global__ __launch_bounds__(256) void loss_reduce_kernel(BiasArgs a) {
-  __shared__ float red[8];
-  const int g = blockIdx.x, tid = threadIdx.x;
-  const int n = a.n;
-  // Only G blocks run, so every loop is latency-bound: the loads are vectorised and the loops
-  // unrolled so one memory round trip serves several iterations (was ~8 us at G = 8).
-  const float* b = a.b + (long)g * n;
-  float bs = 0.f;
-  if ((n & 3) == 0) {
-    const float4* b4 = reinterpret_cast<const float4*>(b);
-#pragma unroll 4
-    for (int j = tid; j < n / 4; j += 256) {
-      const float4 v = b4[j];
-      bs += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-  } else {
-#pragma unroll 4
-    for (int j = tid; j < n; j += 256) bs += b[j] * b[j];
-  }
-  bs = block_sum_256(bs, red);
+// The loss terms of model g (one block of 256 threads): reduces the GEMM-epilogue partials to the
+// reference's loss terms and records |b| = sqrt(bs) of the pre-update bias for the bias-decay
+// term.  `bs` is the caller's block-wide sum of b^2.  Only G blocks run this, so every loop is
+// latency-bound: the loads are vectorised and the loops unrolled so one memory round trip serves
+// several iterations (was ~8 us at G = 8).
+__device__ __forceinline__ void loss_terms(const BiasArgs& a, int g, float bs, float* red) {
+  const int tid = threadIdx.x;
   float l1 = 0.f, l0 = 0.f, se = 0.f;
   const float2* ep = reinterpret_cast<const float2*>(a.enc_part) + (long)g * a.enc_tiles;
 #pragma unroll 4
@@ -151,34 +133,61 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(BiasArgs a) {
     o[3] = l_bd;
     o[4] = l0 / a.B;
     o[5] = bnorm;
-    // the step counter advances once per optimizer step; bias_adam (next launch) reads the new value
-    if (g == 0 && a.update && a.step && !a.defer_step) *a.step += 1;
   }
 }
 
-// Phase 2 (grid: n/32 x G, 256 threads = 8 row-groups x 32 columns): bias gradient from
-// the per-row-tile column partials (each row-group sums every 8th tile, then an LDS
-// reduce -- at a large gathered batch there are B/128 = 128 tiles per column), the
-// bias-decay term, Adam on the bias; optional feature on-count accumulation.
-__global__ __launch_bounds__(256) void bias_adam_kernel(BiasArgs a) {
+// Phase 1 (one block per model): the loss terms, with |b| summed from the bias itself.
+__global__ __launch_bounds__(256) void loss_reduce_kernel(BiasArgs a) {
+  __shared__ float red[8];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int n = a.n;
+  const float* b = a.b + (long)g * n;
+  float bs = 0.f;
+  if ((n & 3) == 0) {
+    const float4* b4 = reinterpret_cast<const float4*>(b);
+#pragma unroll 4
+    for (int j = tid; j < n / 4; j += 256) {
+      const float4 v = b4[j];
+      bs += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+  } else {
+#pragma unroll 4
+    for (int j = tid; j < n; j += 256) bs += b[j] * b[j];
+  }
+  bs = block_sum_256(bs, red);
+  loss_terms(a, g, bs, red);
+  // the step counter advances once per optimizer step; bias_adam (next launch) reads the new value
+  if (tid == 0 && g == 0 && a.step) *a.step += 1;
+}
+
+// Bias Adam on columns [32 bx, 32 bx + 32) of model g (one block: 256 threads = 8 row-groups x 32
+// columns): bias gradient from the per-row-tile column partials (each row-group sums every 8th
+// tile, then an LDS reduce -- at a large gathered batch there are B/128 = 128 tiles per column),
+// the bias-decay term with |b| = bnorm of the pre-update bias, Adam with the bias corrections
+// (bc1, bc2); optional feature on-count accumulation (the on-counts keep the encoder's 128-row
+// slots even when the bias gradient arrives reduced, tm = 1).  True on the threads that own a
+// column (row-group 0, column < n), with the new bias value in `bn`.  (A result the caller can
+// branch on keeps its use of `bn` in the update's own basic block.  With `bn` as the result, the
+// fused tail's moment updates compiled to packed multiplies and adds instead of fused
+// multiply-adds, and rounded differently: profiles/r7/update_refactor/README.md.)
+__device__ __forceinline__ bool bias_adam_cols(const BiasArgs& a, int g, int bx, float bnorm, float bc1, float bc2,
+                                               float& bn) {
   __shared__ float gred[8][33], cred[8][33];
-  const int g = blockIdx.y;
   const int col = threadIdx.x & 31, grp = threadIdx.x >> 5;
-  const int j = blockIdx.x * 32 + col;
+  const int j = bx * 32 + col;
   const int n = a.n;
   const bool ok = j < n;
   const bool counting = a.cnt_part && a.feat_count;
   float gs = 0.f, cs = 0.f;
   if (ok) {
-    if (a.update)
-      for (int t = grp; t < a.tm; t += 8) gs += a.colpart[((long)g * a.tm + t) * n + j];
+    for (int t = grp; t < a.tm; t += 8) gs += a.colpart[((long)g * a.tm + t) * n + j];
     if (counting)
       for (int t = grp; t < a.cnt_tm; t += 8) cs += a.cnt_part[((long)g * a.cnt_tm + t) * n + j];
   }
   gred[grp][col] = gs;
   cred[grp][col] = cs;
   __syncthreads();
-  if (grp != 0 || !ok) return;
+  if (grp != 0 || !ok) return false;
   float gsum = 0.f, csum = 0.f;
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
@@ -187,19 +196,26 @@ __global__ __launch_bounds__(256) void bias_adam_kernel(BiasArgs a) {
   }
   const long idx = (long)g * n + j;
   if (counting) a.feat_count[idx] += csum;
-  if (!a.update) return;
-  const float bnorm = a.out[g * 6 + 5];
   const float beta = a.bias_decay[g];
   const float bd = (beta != 0.f && bnorm > 0.f) ? beta / bnorm : 0.f;
-  float bc1 = a.bc1, bc2 = a.bc2;
-  if (a.step) bias_corrections(a.b1, a.b2, *a.step + a.defer_step, bc1, bc2);
   const float bj = a.b[idx];
   const float gj = gsum * a.gscale + bd * bj;
   const float mj = a.b1 * a.m[idx] + (1.f - a.b1) * gj;
   const float vj = a.b2 * a.v[idx] + (1.f - a.b2) * gj * gj;
   a.m[idx] = mj;
   a.v[idx] = vj;
-  a.b[idx] = bj - (a.lr[g] / bc1) * mj / (sqrtf(vj / bc2) + a.eps);
+  bn = bj - (a.lr[g] / bc1) * mj / (sqrtf(vj / bc2) + a.eps);
+  a.b[idx] = bn;
+  return true;
+}
+
+// Phase 2 (grid: n/32 x G): bias Adam with the |b| loss_reduce recorded and the counter it advanced.
+__global__ __launch_bounds__(256) void bias_adam_kernel(BiasArgs a) {
+  const int g = blockIdx.y;
+  float bc1 = a.bc1, bc2 = a.bc2;
+  if (a.step) bias_corrections(a.b1, a.b2, *a.step, bc1, bc2);
+  float bn;
+  bias_adam_cols(a, g, blockIdx.x, a.out[g * 6 + 5], bc1, bc2, bn);
 }
 
 
@@ -237,38 +253,18 @@ struct TailArgs {
   const float* row_se; int se_rows; float se_scale; float* mse;
 };
 
+// Block-wide sum of b^2 of model g's pre-update bias from the previous step's partials (every
+// block of the model alike).
+__device__ __forceinline__ float tail_bsq(const BiasArgs& a, const TailArgs& t, int g, int par, float* red) {
+  const int nb = a.n / 32;
+  float bs = 0.f;
+  for (int j = threadIdx.x; j < nb; j += 256) bs += t.bsq[((long)par * a.nmodels + g) * nb + j];
+  return block_sum_256(bs, red);
+}
+
 __device__ __forceinline__ void tail_loss(const BiasArgs& a, const TailArgs& t, int g, int par) {
   __shared__ float red[8];
-  const int tid = threadIdx.x, nb = a.n / 32;
-  float bs = 0.f;
-  for (int j = tid; j < nb; j += 256) bs += t.bsq[((long)par * a.nmodels + g) * nb + j];
-  bs = block_sum_256(bs, red);
-  float l1 = 0.f, l0 = 0.f, se = 0.f;
-  const float2* ep = reinterpret_cast<const float2*>(a.enc_part) + (long)g * a.enc_tiles;
-#pragma unroll 4
-  for (int k = tid; k < a.enc_tiles; k += 256) {
-    const float2 v = ep[k];
-    l1 += v.x;
-    l0 += v.y;
-  }
-#pragma unroll 4
-  for (int k = tid; k < a.dec_tiles; k += 256) se += a.dec_part[(long)g * a.dec_tiles + k];
-  l1 = block_sum_256(l1, red);
-  l0 = block_sum_256(l0, red);
-  se = block_sum_256(se, red);
-  if (tid == 0) {
-    const float bnorm = sqrtf(bs);
-    const float l_rec = se / ((float)a.B * a.d);
-    const float l_l1 = a.l1[g] * l1 / a.B;
-    const float l_bd = a.bias_decay[g] * bnorm;
-    float* o = a.out + g * 6;
-    o[0] = l_rec + l_l1 + l_bd;
-    o[1] = l_rec;
-    o[2] = l_l1;
-    o[3] = l_bd;
-    o[4] = l0 / a.B;
-    o[5] = bnorm;
-  }
+  loss_terms(a, g, tail_bsq(a, t, g, par, red), red);
 }
 
 __device__ __forceinline__ void tail_mse(const TailArgs& t, int g) {
@@ -282,50 +278,29 @@ __device__ __forceinline__ void tail_mse(const TailArgs& t, int g) {
 }
 
 __device__ __forceinline__ void tail_bias(const BiasArgs& a, const TailArgs& t, int bx, int g, int step, int par) {
-  __shared__ float gred[8][33], cred[8][33], sred[8];
-  const int col = threadIdx.x & 31, grp = threadIdx.x >> 5;
-  const int n = a.n, nb = n / 32;
-  const int j = bx * 32 + col;
-  const bool counting = a.cnt_part && a.feat_count;
-  // |b| of the pre-update bias from the previous step's partials (every block of the model alike)
-  float bs = 0.f;
-  for (int k = threadIdx.x; k < nb; k += 256) bs += t.bsq[((long)par * a.nmodels + g) * nb + k];
-  bs = block_sum_256(bs, sred);
-  float gs = 0.f, cs = 0.f;
-  for (int k = grp; k < a.tm; k += 8) gs += a.colpart[((long)g * a.tm + k) * n + j];
-  // (on-counts keep the encoder's 128-row slots even when the bias gradient arrives reduced, tm = 1)
-  if (counting)
-    for (int k = grp; k < a.cnt_tm; k += 8) cs += a.cnt_part[((long)g * a.cnt_tm + k) * n + j];
-  gred[grp][col] = gs;
-  cred[grp][col] = cs;
-  __syncthreads();
-  if (grp != 0) return;
-  float gsum = 0.f, csum = 0.f;
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    gsum += gred[r][col];
-    csum += cred[r][col];
-  }
-  const long idx = (long)g * n + j;
-  if (counting) a.feat_count[idx] += csum;
-  const float bnorm = sqrtf(bs);
-  const float beta = a.bias_decay[g];
-  const float bd = (beta != 0.f && bnorm > 0.f) ? beta / bnorm : 0.f;
+  __shared__ float sred[8];
+  const float bs = tail_bsq(a, t, g, par, sred);
   float bc1, bc2;
   bias_corrections(a.b1, a.b2, step + 1, bc1, bc2);
-  const float bj = a.b[idx];
-  const float gj = gsum * a.gscale + bd * bj;
-  const float mj = a.b1 * a.m[idx] + (1.f - a.b1) * gj;
-  const float vj = a.b2 * a.v[idx] + (1.f - a.b2) * gj * gj;
-  a.m[idx] = mj;
-  a.v[idx] = vj;
-  const float bn = bj - (a.lr[g] / bc1) * mj / (sqrtf(vj / bc2) + a.eps);
-  a.b[idx] = bn;
+  float bn;
+  if (!bias_adam_cols(a, g, bx, sqrtf(bs), bc1, bc2, bn)) return;
   // this block's 32 columns of |b_new|^2 for the next step (lanes 0-31 of wave 0)
   float sq = bn * bn;
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 32);
-  if (col == 0) t.bsq[((long)(par ^ 1) * a.nmodels + g) * nb + bx] = sq;
+  if (threadIdx.x == 0) t.bsq[((long)(par ^ 1) * a.nmodels + g) * (a.n / 32) + bx] = sq;
+}
+
+// Row r of the next step's batch (one wave): out[r] = buf[perm[(step + 1 - ep0) * rows + r]].
+__device__ __forceinline__ void tail_gather(const TailArgs& t, int step, long r) {
+  if (r >= t.grows) return;
+  const int lane = threadIdx.x & 63;
+  const long jj = (long)(step + 1 - t.ep0[0]) * t.grows + r;
+  long src = (jj >= 0 && jj < t.nperm) ? t.perm[jj] : 0;
+  src = (src >= 0 && src < t.nbuf) ? src : 0;
+  const u32x4_t* sp = t.gbuf + src * t.row_vec;
+  u32x4_t* op = t.gout + r * t.row_vec;
+  for (int v = lane; v < t.row_vec; v += 64) op[v] = sp[v];
 }
 
 template <int NV, bool GBF>
@@ -343,16 +318,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(AdamArgs a, BiasArgs b, 
     // the next step's batch: the LAST blocks dispatched, so the rows are written at the end of the
     // launch and still sit in L2 when the next step's encoder reads them (written first, the Adam
     // stream evicted them: encoder 67 vs 57 us, measured)
-    const long r = (long)(bid - ((int)gridDim.x - t.ngather)) * 4 + (threadIdx.x >> 6);
-    if (r < t.grows) {
-      const int lane = threadIdx.x & 63;
-      const long jj = (long)(step + 1 - t.ep0[0]) * t.grows + r;
-      long src = (jj >= 0 && jj < t.nperm) ? t.perm[jj] : 0;
-      src = (src >= 0 && src < t.nbuf) ? src : 0;
-      const u32x4_t* sp = t.gbuf + src * t.row_vec;
-      u32x4_t* op = t.gout + r * t.row_vec;
-      for (int v = lane; v < t.row_vec; v += 64) op[v] = sp[v];
-    }
+    tail_gather(t, step, (long)(bid - ((int)gridDim.x - t.ngather)) * 4 + (threadIdx.x >> 6));
   } else {
     long r = (long)(bid - t.nloss - t.nbias) * 4 + (threadIdx.x >> 6);
     if (t.lcomp) {  // compacted masked grid: skip the dead rows' blocks altogether
@@ -390,6 +356,51 @@ __global__ __launch_bounds__(256) void step_tail_kernel(AdamArgs a, BiasArgs b, 
   }
 }
 
+// ------------------------------------------------------------------ host side
+// Fills the row-Adam arguments from the per-set pointer arrays; returns the total row count.
+static long fill_adam(AdamArgs& a, int nset, float* const* p, const void* const* g, float* const* m,
+                      float* const* v, void* const* shadow, float* const* norms, const int* rows, const int* norm,
+                      int d, int rows_per_model, const float* lr, float b1, float b2, float eps, float bc1,
+                      float bc2, const int* step, int nsplit, long gstride, long row0, const int* live) {
+  long total = 0;
+  for (int i = 0; i < nset; ++i) {
+    a.set[i] = {p[i], g[i], m[i], v[i], reinterpret_cast<uint16_t*>(shadow[i]), norms[i], rows[i], norm[i]};
+    total += rows[i];
+  }
+  if (nset == 1) a.set[1] = a.set[0], a.set[1].rows = 0;
+  a.nset = nset; a.d = d; a.rows_per_model = rows_per_model; a.lr = lr;
+  a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = bc1; a.bc2 = bc2; a.step = step;
+  a.nsplit = nsplit; a.gstride = gstride; a.row0 = row0; a.live = live;
+  return total;
+}
+
+// Fills the next-batch gather of a step tail (gbuf == nullptr: none); false if the rows cannot be
+// copied as 16-byte vectors.
+static bool fill_gather(TailArgs& t, const void* gbuf, long nbuf, const long* perm, long nperm, const int* ep0,
+                        void* gout, long grows, long row_bytes) {
+  if (gbuf && (row_bytes % 16 || nbuf < 1)) return false;
+  t.gbuf = reinterpret_cast<const u32x4_t*>(gbuf); t.nbuf = nbuf; t.perm = perm; t.nperm = nperm; t.ep0 = ep0;
+  t.gout = reinterpret_cast<u32x4_t*>(gout); t.grows = gbuf ? grows : 0;
+  t.row_vec = (int)(row_bytes / 16);
+  t.ngather = gbuf ? (int)((grows + 3) / 4) : 0;
+  return true;
+}
+
+static int launch_tail(int d, int gbf16, long blocks, hipStream_t stream, const AdamArgs& a, const BiasArgs& ba,
+                       const TailArgs& t) {
+#define SC_TAIL(NVV)                                                                                   \
+  case NVV:                                                                                            \
+    if (gbf16) hipLaunchKernelGGL((step_tail_kernel<NVV, true>), dim3(blocks), dim3(256), 0, stream, a, ba, t); \
+    else hipLaunchKernelGGL((step_tail_kernel<NVV, false>), dim3(blocks), dim3(256), 0, stream, a, ba, t);      \
+    break;
+  switch (d / 256) {
+    SC_TAIL(1) SC_TAIL(2) SC_TAIL(3) SC_TAIL(4)
+    default: return 1;
+  }
+#undef SC_TAIL
+  return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
 }  // namespace scamd
 
 using namespace scamd;
@@ -403,15 +414,8 @@ int sc_adam_rows(int nset, float* const* p, const void* const* g, float* const* 
                  const int* live, int gbf16) {
   if (d % 256 || d > 4096 || nset < 1 || nset > 2 || nsplit < 1) return 1;
   AdamArgs a;
-  long total = 0;
-  for (int i = 0; i < nset; ++i) {
-    a.set[i] = {p[i], g[i], m[i], v[i], reinterpret_cast<uint16_t*>(shadow[i]), norms[i], rows[i], norm[i]};
-    total += rows[i];
-  }
-  if (nset == 1) a.set[1] = a.set[0], a.set[1].rows = 0;
-  a.nset = nset; a.d = d; a.rows_per_model = rows_per_model; a.lr = lr;
-  a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = bc1; a.bc2 = bc2; a.step = step;
-  a.nsplit = nsplit; a.gstride = gstride; a.row0 = row0; a.live = live;
+  const long total = fill_adam(a, nset, p, g, m, v, shadow, norms, rows, norm, d, rows_per_model, lr, b1, b2, eps,
+                               bc1, bc2, step, nsplit, gstride, row0, live);
   const long blocks = (total + 3) / 4;
   // bf16 gradients: plain loads only (the NT knob A/B'd slower, profiles/)
 #define SC_ADAM(NVV)                                                                                  \
@@ -439,18 +443,16 @@ int sc_bias_loss(int G, float* b, float* m, float* v, const float* colpart, int 
                  const float* enc_part, int enc_tiles, const float* dec_part, int dec_tiles,
                  const float* cnt_part, float* feat_count, const float* l1, const float* bias_decay,
                  const float* lr, float* out, int n, int B, int d, float gscale, float b1, float b2, float eps,
-                 float bc1, float bc2, int update, int* step, hipStream_t stream, int defer_step, int cnt_tm) {
+                 float bc1, float bc2, int* step, hipStream_t stream, int cnt_tm) {
   BiasArgs a;
   a.b = b; a.m = m; a.v = v; a.colpart = colpart; a.tm = tm;
   a.enc_part = enc_part; a.enc_tiles = enc_tiles; a.dec_part = dec_part; a.dec_tiles = dec_tiles;
   a.cnt_part = cnt_part; a.feat_count = feat_count; a.cnt_tm = cnt_tm > 0 ? cnt_tm : tm;
   a.l1 = l1; a.bias_decay = bias_decay; a.lr = lr; a.out = out;
   a.n = n; a.B = B; a.d = d; a.nmodels = G; a.gscale = gscale;
-  a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = bc1; a.bc2 = bc2; a.update = update; a.step = step;
-  a.defer_step = defer_step ? 1 : 0;
+  a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = bc1; a.bc2 = bc2; a.step = step;
   hipLaunchKernelGGL(loss_reduce_kernel, dim3(G), dim3(256), 0, stream, a);
-  if (update || (cnt_part && feat_count))
-    hipLaunchKernelGGL(bias_adam_kernel, dim3((n + 31) / 32, G), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(bias_adam_kernel, dim3((n + 31) / 32, G), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
@@ -467,19 +469,11 @@ int sc_step_tail(int nset, float* const* p, const void* const* g, float* const* 
                  const int* ep0, void* gout, long grows, long row_bytes, int nsplit, long gstride,
                  const int* live, int cnt_tm, long row0, const int* live_h, hipStream_t stream) {
   if (d % 256 || d > 4096 || nset < 1 || nset > 2 || n % 32 || !step || !ticket || !bsq || nsplit < 1) return 1;
-  if (gbuf && (row_bytes % 16 || nbuf < 1)) return 1;
   AdamArgs a;
-  long total = 0;
-  for (int i = 0; i < nset; ++i) {
-    a.set[i] = {p[i], g[i], m[i], v[i], reinterpret_cast<uint16_t*>(shadow[i]), norms[i], rows[i], norm[i]};
-    total += rows[i];
-  }
-  if (nset == 1) a.set[1] = a.set[0], a.set[1].rows = 0;
-  a.nset = nset; a.d = d; a.rows_per_model = rows_per_model; a.lr = lr;
-  a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = 1.f; a.bc2 = 1.f; a.step = step;
   // live: masked ensembles (may be null); row0: the sets are rows [row0, row0 + rows) of the
   // [G n] stack (a ZeRO-1 shard; the loss and bias roles still cover every model)
-  a.nsplit = nsplit; a.gstride = gstride; a.row0 = row0; a.live = live;
+  const long total = fill_adam(a, nset, p, g, m, v, shadow, norms, rows, norm, d, rows_per_model, lr, b1, b2, eps,
+                               1.f, 1.f, step, nsplit, gstride, row0, live);
   BiasArgs ba;
   ba.b = b; ba.m = bm; ba.v = bv; ba.colpart = colpart; ba.tm = tm;
   ba.enc_part = enc_part; ba.enc_tiles = enc_tiles; ba.dec_part = dec_part; ba.dec_tiles = dec_tiles;
@@ -488,16 +482,12 @@ int sc_step_tail(int nset, float* const* p, const void* const* g, float* const* 
   ba.cnt_part = cnt_part; ba.feat_count = feat_count; ba.cnt_tm = cnt_tm > 0 ? cnt_tm : tm;
   ba.l1 = l1; ba.bias_decay = bias_decay; ba.lr = lr; ba.out = out;
   ba.n = n; ba.B = B; ba.d = d; ba.nmodels = G; ba.gscale = gscale;
-  ba.b1 = b1; ba.b2 = b2; ba.eps = eps; ba.bc1 = 1.f; ba.bc2 = 1.f; ba.update = 1; ba.step = step;
-  ba.defer_step = 0;
-  TailArgs t;
+  ba.b1 = b1; ba.b2 = b2; ba.eps = eps; ba.bc1 = 1.f; ba.bc2 = 1.f; ba.step = step;
+  TailArgs t = {};
+  if (!fill_gather(t, gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes)) return 1;
   t.bsq = bsq; t.ticket = ticket;
-  t.gbuf = reinterpret_cast<const u32x4_t*>(gbuf); t.nbuf = nbuf; t.perm = perm; t.nperm = nperm; t.ep0 = ep0;
-  t.gout = reinterpret_cast<u32x4_t*>(gout); t.grows = gbuf ? grows : 0;
-  t.row_vec = (int)(row_bytes / 16);
-  t.nloss = G; t.nbias = G * (n / 32); t.ngather = gbuf ? (int)((grows + 3) / 4) : 0;
-  t.lcomp = 0; t.lG = G;
-  t.row_se = nullptr; t.se_rows = 0; t.se_scale = 0.f; t.mse = nullptr;
+  t.nloss = G; t.nbias = G * (n / 32);
+  t.lG = G;
   long arows = total;
   // host copy of a masked ensemble's live sizes (full-stack sets only, G <= 16): launch live rows only
   if (live_h && live && row0 == 0 && G <= 16 && rows_per_model > 0 && rows[0] == (long)G * rows_per_model &&
@@ -512,17 +502,7 @@ int sc_step_tail(int nset, float* const* p, const void* const* g, float* const* 
     }
   }
   const long blocks = t.nloss + t.nbias + t.ngather + (arows + 3) / 4;
-#define SC_TAIL(NVV)                                                                                   \
-  case NVV:                                                                                            \
-    if (gbf16) hipLaunchKernelGGL((step_tail_kernel<NVV, true>), dim3(blocks), dim3(256), 0, stream, a, ba, t); \
-    else hipLaunchKernelGGL((step_tail_kernel<NVV, false>), dim3(blocks), dim3(256), 0, stream, a, ba, t);      \
-    break;
-  switch (d / 256) {
-    SC_TAIL(1) SC_TAIL(2) SC_TAIL(3) SC_TAIL(4)
-    default: return 1;
-  }
-#undef SC_TAIL
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return launch_tail(d, gbf16, blocks, stream, a, ba, t);
 }
 
 // Top-k step tail (engine/topk.py): row Adam with the norm Jacobian over the [G n, d] dictionary stack
@@ -535,36 +515,20 @@ int sc_topk_tail(float* p, const void* g, float* m, float* v, void* shadow, floa
                  const long* perm, long nperm, const int* ep0, void* gout, long grows, long row_bytes,
                  hipStream_t stream) {
   if (d % 256 || d > 1024 || G < 1 || n < 1 || !step || !ticket || !row_se || !mse || se_rows < 1) return 1;
-  if (gbuf && (row_bytes % 16 || nbuf < 1)) return 1;
   AdamArgs a;
-  a.set[0] = {p, g, m, v, reinterpret_cast<uint16_t*>(shadow), norms, G * n, 1};
-  a.set[1] = a.set[0];
-  a.set[1].rows = 0;
-  a.nset = 1; a.d = d; a.rows_per_model = n; a.lr = lr;
-  a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = 1.f; a.bc2 = 1.f; a.step = step;
-  a.nsplit = 1; a.gstride = 0; a.row0 = 0; a.live = nullptr;
+  const int rows = G * n, norm = 1;
+  fill_adam(a, 1, &p, &g, &m, &v, &shadow, &norms, &rows, &norm, d, n, lr, b1, b2, eps, 1.f, 1.f, step, 1, 0, 0,
+            nullptr);
   BiasArgs ba = {};
   ba.step = step; ba.nmodels = G; ba.n = n;
   TailArgs t = {};
+  if (!fill_gather(t, gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes)) return 1;
   t.ticket = ticket;
-  t.gbuf = reinterpret_cast<const u32x4_t*>(gbuf); t.nbuf = nbuf; t.perm = perm; t.nperm = nperm; t.ep0 = ep0;
-  t.gout = reinterpret_cast<u32x4_t*>(gout); t.grows = gbuf ? grows : 0;
-  t.row_vec = (int)(row_bytes / 16);
-  t.nloss = G; t.nbias = 0; t.ngather = gbuf ? (int)((grows + 3) / 4) : 0;
-  t.lcomp = 0; t.lG = G;
+  t.nloss = G;
+  t.lG = G;
   t.row_se = row_se; t.se_rows = se_rows; t.se_scale = se_scale; t.mse = mse;
   const long blocks = t.nloss + t.ngather + ((long)G * n + 3) / 4;
-#define SC_TAIL(NVV)                                                                                   \
-  case NVV:                                                                                            \
-    if (gbf16) hipLaunchKernelGGL((step_tail_kernel<NVV, true>), dim3(blocks), dim3(256), 0, stream, a, ba, t); \
-    else hipLaunchKernelGGL((step_tail_kernel<NVV, false>), dim3(blocks), dim3(256), 0, stream, a, ba, t);      \
-    break;
-  switch (d / 256) {
-    SC_TAIL(1) SC_TAIL(2) SC_TAIL(3) SC_TAIL(4)
-    default: return 1;
-  }
-#undef SC_TAIL
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return launch_tail(d, gbf16, blocks, stream, a, ba, t);
 }
 
 }  // extern "C"

@@ -192,13 +192,7 @@ class FusedChunk:
 
         e = self.engine
 
-        def run():
-            if e.kind == "threshold" or e.learned_center:
-                e._threshold_extra_adam(reduced=True)
-            e.adam_rows_all()
-            e._bias_loss(update=True, reduced=True)
-
-        graphed_region(self, "update", run)
+        graphed_region(self, "update", lambda: e.update(reduced=True, fused=False))
         e._host_step()
         return e.out
 

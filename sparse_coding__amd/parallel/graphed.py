@@ -30,8 +30,6 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from ..ops import adam as adam_ops
-
 from .dist import DistInfo
 from .zero import shard_range
 
@@ -140,20 +138,10 @@ class GraphedDataParallel:
         self._wait(c.red_ev)
         c.red_ev = None
         if self.mode == "dp":
-            if e._tail_ok:
-                # the fused step tail (row Adam + losses + bias Adam, one launch) on the all-reduced
-                # gradients: the bias gradient arrives reduced and scaled ([G, 1, n], gscale 1)
-                adam_ops.step_tail(e._adam_sets(), e.lr, *e.betas, e.eps, e.step_dev, e.params[e._bkey],
-                                   e.m[e._bkey], e.v[e._bkey], e.g_bias, e.enc_part, e.dec_part, e.l1,
-                                   e.bias_decay, e.out, e.batch_size, 1.0, e._bsq, e._ticket,
-                                   cnt_part=e.cnt_part if e._counted else None,
-                                   feat_count=e.feature_counts if e._counted else None, live=e.nactive,
-                                   gather=gather)
-            else:
-                e.adam_rows_all()
-                e._bias_loss(update=True, reduced=True)
+            # on the all-reduced gradients: the bias gradient arrives reduced and scaled
+            e.update(reduced=True, gather=gather)
             return
-        G, n, d = e.n_models, e.n, e.d
+        d = e.d
         lo, hi = c.lo, c.hi
         if c.world == 1:  # one rank: the shard is the whole gradient
             grads = c.srcs
@@ -162,28 +150,9 @@ class GraphedDataParallel:
                 for i, dst in enumerate(c.shards):
                     torch.sum(c.recv[i].view(c.world, -1), dim=0, dtype=torch.float32, out=dst.view(-1))
             grads = c.shards
-        rows = lambda t: t.view(G * n, d)[lo:hi]  # noqa: E731
-        g = [gg.view(-1, d) if c.world == 1 else gg for gg in grads]
-        if e.kind == "untied":
-            sets = [dict(p=rows(e.params["decoder"]), g=rows(g[0]) if c.world == 1 else g[0], m=rows(e.m["decoder"]),
-                         v=rows(e.v["decoder"]), shadow=rows(e.dec_shadow), norms=e.norms.view(-1)[lo:hi], norm=True),
-                    dict(p=rows(e.params["encoder"]), g=rows(g[1]) if c.world == 1 else g[1], m=rows(e.m["encoder"]),
-                         v=rows(e.v["encoder"]), shadow=rows(e.enc_shadow), norms=None, norm=False)]
-        else:
-            sets = [dict(p=rows(e.params["encoder"]), g=rows(g[0]) if c.world == 1 else g[0], m=rows(e.m["encoder"]),
-                         v=rows(e.v["encoder"]), shadow=rows(e.enc_shadow), norms=e.norms.view(-1)[lo:hi], norm=True)]
-        if e._tail_ok:
-            # the fused step tail on the owned rows (row Adam) + every model's losses and bias Adam
-            # (the bias gradient arrives all-reduced and scaled)
-            adam_ops.step_tail(sets, e.lr, *e.betas, e.eps, e.step_dev, e.params[e._bkey], e.m[e._bkey],
-                               e.v[e._bkey], e.g_bias, e.enc_part, e.dec_part, e.l1, e.bias_decay, e.out,
-                               e.batch_size, 1.0, e._bsq, e._ticket, cnt_part=e.cnt_part if e._counted else None,
-                               feat_count=e.feature_counts if e._counted else None, row0=lo, gather=gather,
-                               live=e.nactive)
-        else:
-            adam_ops.adam_rows(sets, e.lr, e.step_count + 1, *e.betas, e.eps, rows_per_model=n,
-                               step_dev=e.step_dev, row0=lo, live=e.nactive)
-            e._bias_loss(update=True, reduced=True)
+        # row Adam on the owned rows + every model's losses and bias Adam (the bias gradient arrives
+        # all-reduced and scaled)
+        e.update(e.row_sets(lo, hi, grads), reduced=True, row0=lo, gather=gather)
         if c.world > 1:  # every rank's updated shadows (and norms) for the chunk's next compute
             evs = []
             for sh in ([e.dec_shadow] if e.kind == "untied" else []) + [e.enc_shadow]:

@@ -245,36 +245,16 @@ class ZeroFusedChunk:
 
     def apply_update(self, _payload=None):
         e = self.engine
-
-        def run():
-            self._shard_adam()
-            e._bias_loss(update=True, reduced=True)
-
-        self._region("update", run)
+        grads = [self.g_dec_shard] + ([self.g_enc_shard] if e.kind == "untied" else [])
+        # shard Adam on the owned rows, then every model's losses and bias Adam
+        self._region("update", lambda: e.update(e.row_sets(self.lo, self.hi, grads), reduced=True, row0=self.lo,
+                                                fused=False))
         e._host_step()
         self._issue_gathers()
         self.steps += 1
         return e.out
 
     # ------------------------------------------------------------------ internals
-    def _shard_adam(self):
-        from ..ops import adam as adam_ops
-
-        e = self.engine
-        G, n, d = e.n_models, e.n, e.d
-        lo, hi = self.lo, self.hi
-        rows = lambda t: t.view(G * n, d)[lo:hi]  # noqa: E731
-        if e.kind == "untied":
-            sets = [dict(p=rows(e.params["decoder"]), g=self.g_dec_shard, m=rows(e.m["decoder"]),
-                         v=rows(e.v["decoder"]), shadow=rows(e.dec_shadow), norms=e.norms.view(-1)[lo:hi], norm=True),
-                    dict(p=rows(e.params["encoder"]), g=self.g_enc_shard, m=rows(e.m["encoder"]),
-                         v=rows(e.v["encoder"]), shadow=rows(e.enc_shadow), norms=None, norm=False)]
-        else:
-            sets = [dict(p=rows(e.params["encoder"]), g=self.g_dec_shard, m=rows(e.m["encoder"]),
-                         v=rows(e.v["encoder"]), shadow=rows(e.enc_shadow), norms=e.norms.view(-1)[lo:hi], norm=True)]
-        adam_ops.adam_rows(sets, e.lr, e.step_count + 1, *e.betas, e.eps, rows_per_model=n, step_dev=e.step_dev,
-                           row0=lo, live=e.nactive)
-
     def _issue_gathers(self):
         if self._solo:
             return

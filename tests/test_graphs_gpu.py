@@ -115,7 +115,7 @@ def test_prime_source_captures_without_running():
 
 
 @pytest.mark.parametrize("kind,G,B", [("untied", 3, 256), ("tied", 3, 256), ("untied", 1, 4096)])
-def test_fused_step_tail_matches_separate_kernels(kind, G, B, monkeypatch):
+def test_fused_step_tail_matches_separate_kernels(kind, G, B):
     """The fused step tail (row Adam + loss terms + bias Adam + step counter in one launch, |b| from
     parity-double-buffered b^2 partials) against the separate adam_rows / loss_reduce / bias_adam
     kernels: parameters, moments, losses, feature counts and the device step counter, over eager steps
@@ -131,8 +131,7 @@ def test_fused_step_tail_matches_separate_kernels(kind, G, B, monkeypatch):
     for p, _ in models:
         p["encoder_bias"].normal_(0.0, 0.1)
     a = FusedSAEEnsemble(models, sig, lr=1e-3, batch_size=B, device=DEV, count_every=2)
-    monkeypatch.setenv("SC_FUSED_TAIL", "0")
-    b = FusedSAEEnsemble(models, sig, lr=1e-3, batch_size=B, device=DEV, count_every=2)
+    b = FusedSAEEnsemble(models, sig, lr=1e-3, batch_size=B, device=DEV, count_every=2, fused_tail=False)
     assert a._tail_ok and not b._tail_ok
     assert (a.wsplit > 1) == (G == 1)  # one model on a large batch: split-K gradient slabs into the tail
     feats = torch.nn.functional.normalize(torch.randn(2048, d, device=DEV), dim=-1)

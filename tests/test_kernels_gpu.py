@@ -533,9 +533,8 @@ def test_topk_tail_matches_separate_launches():
     torch.manual_seed(23)
     d, n, B = 768, 1024, 256
     models = [TopKEncoder.init(d, n, k, device=DEV) for k in (4, 16, 64)]
-    fused, split = (FusedTopKEnsemble(models, batch_size=B, device=DEV, lr=1e-3) for _ in range(2))
-    assert fused._tail
-    split._tail = False
+    fused, split = (FusedTopKEnsemble(models, batch_size=B, device=DEV, lr=1e-3, fused_tail=ft) for ft in (True, False))
+    assert fused._tail and not split._tail
     for t in range(3):
         x = torch.randn(B, d, device=DEV).to(torch.bfloat16)
         mf, ms = fused.step_batch(x).clone(), split.step_batch(x).clone()
