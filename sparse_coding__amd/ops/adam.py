@@ -3,10 +3,44 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
 from . import _lib
+
+
+# Launch policy of the row-Adam kernels (csrc/adam.hip, csrc/row_adam.h): bit 0 streams the fp32 p / m / v
+# loads, bit 1 their stores (non-temporal; touched once per step, they only cost the GEMM operands their
+# place in the caches).  Cache hints only: every policy writes the same bits.  Both, on the headline step:
+# 0.2682 vs 0.2820 ms; either alone gains nothing (profiles/r8/tail_cache/README.md).
+POLICY_NT_LOAD, POLICY_NT_STORE = 1, 2
+DEFAULT_POLICY = POLICY_NT_LOAD | POLICY_NT_STORE
+
+
+def _env_policy():
+    """``SC_TAIL_POLICY=<0..3>`` overrides the default policy, for same-box A/B runs of whole steps
+    (read once, at import)."""
+    spec = os.environ.get("SC_TAIL_POLICY", "").strip()
+    pol = int(spec) if spec else DEFAULT_POLICY
+    if not 0 <= pol <= 3:
+        raise ValueError(f"SC_TAIL_POLICY must be in 0..3 (got {spec!r})")
+    return pol
+
+
+_POLICY = _env_policy()
+
+
+def policy() -> int:
+    return _POLICY
+
+
+def set_policy(pol: int):
+    """Select the launch policy of the following row-Adam launches (tests / A-B timing)."""
+    global _POLICY
+    if not 0 <= int(pol) <= 3:
+        raise ValueError(f"policy must be in 0..3 (got {pol})")
+    _POLICY = int(pol)
 
 
 def _vp(seq):
@@ -87,7 +121,7 @@ def adam_rows(sets, lr, step, b1=0.9, b2=0.999, eps=1e-8, rows_per_model=None, s
         _vp([s.get("shadow") for s in sets]), _vp([s.get("norms") for s in sets]),
         rows, norm, d, rpm, _lib.ptr(lr), b1, b2, eps, bc1, bc2,
         _lib.ptr(step_dev), int(nsplit), int(gstride), int(row0), _lib.stream_handle(), _lib.ptr(live),
-        int(gbf16),
+        int(gbf16), _POLICY,
     )
     _lib.check(rc, "sc_adam_rows")
 
@@ -174,7 +208,7 @@ def step_tail(sets, lr, b1, b2, eps, step_dev, bias, bias_m, bias_v, colpart, en
         gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes,
         int(nsplit), int(gstride), _lib.ptr(live), int(cnt_tm), int(row0 or 0),
         C.cast((C.c_int * len(live_host))(*[int(v) for v in live_host]), C.c_void_p)
-        if (live_host is not None and live is not None) else None, _lib.stream_handle(),
+        if (live_host is not None and live is not None) else None, _lib.stream_handle(), _POLICY,
     )
     _lib.check(rc, "sc_step_tail")
 
@@ -205,7 +239,7 @@ def topk_tail(p, g, m, v, shadow, norms, lr, b1, b2, eps, step_dev, row_se, mse,
         _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), _lib.ptr(shadow), _lib.ptr(norms), G, n, d,
         _lib.ptr(lr), b1, b2, eps, _lib.ptr(step_dev), int(gbf16), _lib.ptr(row_se), row_se.shape[1],
         float(se_scale), _lib.ptr(mse), _lib.ptr(ticket), gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes,
-        _lib.stream_handle(),
+        _lib.stream_handle(), _POLICY,
     )
     _lib.check(rc, "sc_topk_tail")
 

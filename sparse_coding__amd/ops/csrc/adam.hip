@@ -44,7 +44,13 @@ struct AdamArgs {
   const int* live;  // optional per-model live row count (masked ensembles): rows past it are skipped
 };
 
-template <int NV, bool GBF = false>
+// The row-Adam kernels are templated on a launch policy POL (one integer argument of sc_step_tail /
+// sc_topk_tail / sc_adam_rows; ops/adam.py reads it once from SC_TAIL_POLICY): POL_NT_LOAD |
+// POL_NT_STORE (row_adam.h).  (An XCD-affine, model-major order of the tail's row blocks, so that the
+// XCD that reads model g's shadows next step writes them, lost on the headline, 0.2865 vs 0.2820 ms
+// alone and nothing on top of the streamed accesses: scripts/lab/tail_cache_r8.patch,
+// profiles/r8/tail_cache/README.md.)
+template <int NV, bool GBF = false, int POL = 0>
 __device__ __forceinline__ void adam_row(const AdamArgs& a, long wave) {
   const int lane = threadIdx.x & 63;
   long row = wave;
@@ -60,13 +66,13 @@ __device__ __forceinline__ void adam_row(const AdamArgs& a, long wave) {
   const float lr = a.lr[grow / a.rows_per_model];
   float bc1 = a.bc1, bc2 = a.bc2;
   if (a.step) bias_corrections(a.b1, a.b2, *a.step + 1, bc1, bc2);
-  adam_row_core<NV, GBF>(R.p, R.g, R.m, R.v, R.shadow, R.norms, row, R.norm, a.nsplit, a.gstride, lr, a.b1, a.b2,
-                         a.eps, bc1, bc2, lane);
+  adam_row_core<NV, GBF, POL>(R.p, R.g, R.m, R.v, R.shadow, R.norms, row, R.norm, a.nsplit, a.gstride, lr, a.b1, a.b2,
+                              a.eps, bc1, bc2, lane);
 }
 
-template <int NV, bool GBF = false>
+template <int NV, bool GBF = false, int POL = 0>
 __global__ __launch_bounds__(256) void adam_rows_kernel(AdamArgs a) {
-  adam_row<NV, GBF>(a, (long)blockIdx.x * 4 + (threadIdx.x >> 6));
+  adam_row<NV, GBF, POL>(a, (long)blockIdx.x * 4 + (threadIdx.x >> 6));
 }
 
 // Writes a bf16 (optionally row-normalised) shadow of fp32 rows; used at init
@@ -136,14 +142,36 @@ __device__ __forceinline__ void loss_terms(const BiasArgs& a, int g, float bs, f
   }
 }
 
-// Phase 1 (one block per model): the loss terms, with |b| summed from the bias itself.
+// Sum of x^2 over the 32 columns of one bias block (32 lanes, every lane gets the total): the b^2 partial
+// the fused tail keeps per 32 columns, and the order in which loss_reduce_kernel sums |b|^2, so that
+// the separate kernels and the tail agree on |b| to the bit.
+__device__ __forceinline__ float sq_sum_32(float x) {
+  float sq = __fmul_rn(x, x);
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 32);
+  return sq;
+}
+
+constexpr int LR_PARTS = 2048;  // loss_reduce_kernel: b^2 partials it can hold (n <= 65536)
+
+// Phase 1 (one block per model): the loss terms, with |b| summed from the bias itself -- in the fused
+// tail's order (per-32-column partials, then tail_bsq's sum over them) wherever a tail could run.
 __global__ __launch_bounds__(256) void loss_reduce_kernel(BiasArgs a) {
   __shared__ float red[8];
+  __shared__ float part[LR_PARTS];
   const int g = blockIdx.x, tid = threadIdx.x;
   const int n = a.n;
   const float* b = a.b + (long)g * n;
   float bs = 0.f;
-  if ((n & 3) == 0) {
+  if ((n & 31) == 0 && n / 32 <= LR_PARTS) {
+    const int nb = n / 32;
+    for (int c = tid >> 5; c < nb; c += 8) {
+      const float sq = sq_sum_32(b[c * 32 + (tid & 31)]);
+      if ((tid & 31) == 0) part[c] = sq;
+    }
+    __syncthreads();
+    for (int j = tid; j < nb; j += 256) bs += part[j];
+  } else if ((n & 3) == 0) {
     const float4* b4 = reinterpret_cast<const float4*>(b);
 #pragma unroll 4
     for (int j = tid; j < n / 4; j += 256) {
@@ -166,7 +194,9 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(BiasArgs a) {
 // the bias-decay term with |b| = bnorm of the pre-update bias, Adam with the bias corrections
 // (bc1, bc2); optional feature on-count accumulation (the on-counts keep the encoder's 128-row
 // slots even when the bias gradient arrives reduced, tm = 1).  True on the threads that own a
-// column (row-group 0, column < n), with the new bias value in `bn`.  (A result the caller can
+// column (row-group 0, column < n), with the new bias value in `bn`.  The gradient and both moment
+// updates are written as the multiply-adds the fused tail compiled them to (the separate bias_adam_kernel
+// used packed multiplies and adds, and differed from the tail in the last bits).  (A result the caller can
 // branch on keeps its use of `bn` in the update's own basic block.  With `bn` as the result, the
 // fused tail's moment updates compiled to packed multiplies and adds instead of fused
 // multiply-adds, and rounded differently: profiles/r7/update_refactor/README.md.)
@@ -199,9 +229,9 @@ __device__ __forceinline__ bool bias_adam_cols(const BiasArgs& a, int g, int bx,
   const float beta = a.bias_decay[g];
   const float bd = (beta != 0.f && bnorm > 0.f) ? beta / bnorm : 0.f;
   const float bj = a.b[idx];
-  const float gj = gsum * a.gscale + bd * bj;
-  const float mj = a.b1 * a.m[idx] + (1.f - a.b1) * gj;
-  const float vj = a.b2 * a.v[idx] + (1.f - a.b2) * gj * gj;
+  const float gj = __fmaf_rn(gsum, a.gscale, bd * bj);
+  const float mj = __fmaf_rn(a.b1, a.m[idx], (1.f - a.b1) * gj);
+  const float vj = __fmaf_rn(a.b2, a.v[idx], (1.f - a.b2) * gj * gj);
   a.m[idx] = mj;
   a.v[idx] = vj;
   bn = bj - (a.lr[g] / bc1) * mj / (sqrtf(vj / bc2) + a.eps);
@@ -285,9 +315,7 @@ __device__ __forceinline__ void tail_bias(const BiasArgs& a, const TailArgs& t, 
   float bn;
   if (!bias_adam_cols(a, g, bx, sqrtf(bs), bc1, bc2, bn)) return;
   // this block's 32 columns of |b_new|^2 for the next step (lanes 0-31 of wave 0)
-  float sq = bn * bn;
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 32);
+  const float sq = sq_sum_32(bn);
   if (threadIdx.x == 0) t.bsq[((long)(par ^ 1) * a.nmodels + g) * (a.n / 32) + bx] = sq;
 }
 
@@ -303,7 +331,7 @@ __device__ __forceinline__ void tail_gather(const TailArgs& t, int step, long r)
   for (int v = lane; v < t.row_vec; v += 64) op[v] = sp[v];
 }
 
-template <int NV, bool GBF>
+template <int NV, bool GBF, int POL>
 __global__ __launch_bounds__(256) void step_tail_kernel(AdamArgs a, BiasArgs b, TailArgs t) {
   const int bid = blockIdx.x;
   const int step = *a.step;          // completed steps before this one (t); read by every block
@@ -331,7 +359,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(AdamArgs a, BiasArgs b, 
         if (k < t.lG && rc >= t.lpre[k]) g = k;
       r = s < a.nset ? (long)s * a.set[0].rows + (long)g * a.rows_per_model + (rc - t.lpre[g]) : a.set[0].rows * 2;
     }
-    adam_row<NV, GBF>(a, r);
+    adam_row<NV, GBF, POL>(a, r);
   }
   // The last block to finish advances the step counter.  Every block's read of *step was consumed
   // (bias corrections, parity) before its ticket, so no fence is needed -- and none is wanted: an
@@ -386,12 +414,23 @@ static bool fill_gather(TailArgs& t, const void* gbuf, long nbuf, const long* pe
   return true;
 }
 
-static int launch_tail(int d, int gbf16, long blocks, hipStream_t stream, const AdamArgs& a, const BiasArgs& ba,
-                       const TailArgs& t) {
-#define SC_TAIL(NVV)                                                                                   \
-  case NVV:                                                                                            \
-    if (gbf16) hipLaunchKernelGGL((step_tail_kernel<NVV, true>), dim3(blocks), dim3(256), 0, stream, a, ba, t); \
-    else hipLaunchKernelGGL((step_tail_kernel<NVV, false>), dim3(blocks), dim3(256), 0, stream, a, ba, t);      \
+template <int NV, bool GBF>
+static void launch_tail_pol(int pol, long blocks, hipStream_t stream, const AdamArgs& a, const BiasArgs& ba,
+                            const TailArgs& t) {
+#define SC_TAIL_POL(P) \
+  case P: hipLaunchKernelGGL((step_tail_kernel<NV, GBF, P>), dim3(blocks), dim3(256), 0, stream, a, ba, t); break;
+  switch (pol) {
+    SC_TAIL_POL(0) SC_TAIL_POL(1) SC_TAIL_POL(2) SC_TAIL_POL(3)
+  }
+#undef SC_TAIL_POL
+}
+
+static int launch_tail(int d, int gbf16, int pol, long blocks, hipStream_t stream, const AdamArgs& a,
+                       const BiasArgs& ba, const TailArgs& t) {
+#define SC_TAIL(NVV)                                                          \
+  case NVV:                                                                   \
+    if (gbf16) launch_tail_pol<NVV, true>(pol, blocks, stream, a, ba, t);     \
+    else launch_tail_pol<NVV, false>(pol, blocks, stream, a, ba, t);          \
     break;
   switch (d / 256) {
     SC_TAIL(1) SC_TAIL(2) SC_TAIL(3) SC_TAIL(4)
@@ -399,6 +438,16 @@ static int launch_tail(int d, int gbf16, long blocks, hipStream_t stream, const 
   }
 #undef SC_TAIL
   return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+template <int NV, bool GBF>
+static void launch_rows_pol(int pol, long blocks, hipStream_t stream, const AdamArgs& a) {
+#define SC_ROWS_POL(P) \
+  case P: hipLaunchKernelGGL((adam_rows_kernel<NV, GBF, P>), dim3(blocks), dim3(256), 0, stream, a); break;
+  switch (pol) {
+    SC_ROWS_POL(0) SC_ROWS_POL(1) SC_ROWS_POL(2) SC_ROWS_POL(3)
+  }
+#undef SC_ROWS_POL
 }
 
 }  // namespace scamd
@@ -411,17 +460,18 @@ int sc_adam_rows(int nset, float* const* p, const void* const* g, float* const* 
                  void* const* shadow, float* const* norms, const int* rows, const int* norm, int d,
                  int rows_per_model, const float* lr, float b1, float b2, float eps, float bc1,
                  float bc2, const int* step, int nsplit, long gstride, long row0, hipStream_t stream,
-                 const int* live, int gbf16) {
-  if (d % 256 || d > 4096 || nset < 1 || nset > 2 || nsplit < 1) return 1;
+                 const int* live, int gbf16, int policy) {
+  if (d % 256 || d > 4096 || nset < 1 || nset > 2 || nsplit < 1 || policy < 0 || policy > 3) return 1;
   AdamArgs a;
   const long total = fill_adam(a, nset, p, g, m, v, shadow, norms, rows, norm, d, rows_per_model, lr, b1, b2, eps,
                                bc1, bc2, step, nsplit, gstride, row0, live);
   const long blocks = (total + 3) / 4;
-  // bf16 gradients: plain loads only (the NT knob A/B'd slower, profiles/)
-#define SC_ADAM(NVV)                                                                                  \
-  case NVV:                                                                                           \
-    if (gbf16) hipLaunchKernelGGL((adam_rows_kernel<NVV, true>), dim3(blocks), dim3(256), 0, stream, a); \
-    else hipLaunchKernelGGL((adam_rows_kernel<NVV>), dim3(blocks), dim3(256), 0, stream, a);            \
+  const int pol = policy;
+  // gradients: plain loads only, whatever the policy (the NT knob on them A/B'd slower, profiles/)
+#define SC_ADAM(NVV)                                                        \
+  case NVV:                                                                 \
+    if (gbf16) launch_rows_pol<NVV, true>(pol, blocks, stream, a);          \
+    else launch_rows_pol<NVV, false>(pol, blocks, stream, a);               \
     break;
   switch (d / 256) {
     SC_ADAM(1) SC_ADAM(2) SC_ADAM(3) SC_ADAM(4) SC_ADAM(6) SC_ADAM(8) SC_ADAM(16)
@@ -467,8 +517,10 @@ int sc_step_tail(int nset, float* const* p, const void* const* g, float* const* 
                  const float* l1, const float* bias_decay, float* out, int n, int B, float gscale,
                  float* bsq, int* ticket, const void* gbuf, long nbuf, const long* perm, long nperm,
                  const int* ep0, void* gout, long grows, long row_bytes, int nsplit, long gstride,
-                 const int* live, int cnt_tm, long row0, const int* live_h, hipStream_t stream) {
-  if (d % 256 || d > 4096 || nset < 1 || nset > 2 || n % 32 || !step || !ticket || !bsq || nsplit < 1) return 1;
+                 const int* live, int cnt_tm, long row0, const int* live_h, hipStream_t stream, int policy) {
+  if (d % 256 || d > 4096 || nset < 1 || nset > 2 || n % 32 || !step || !ticket || !bsq || nsplit < 1 ||
+      policy < 0 || policy > 3)
+    return 1;
   AdamArgs a;
   // live: masked ensembles (may be null); row0: the sets are rows [row0, row0 + rows) of the
   // [G n] stack (a ZeRO-1 shard; the loss and bias roles still cover every model)
@@ -502,7 +554,7 @@ int sc_step_tail(int nset, float* const* p, const void* const* g, float* const* 
     }
   }
   const long blocks = t.nloss + t.nbias + t.ngather + (arows + 3) / 4;
-  return launch_tail(d, gbf16, blocks, stream, a, ba, t);
+  return launch_tail(d, gbf16, policy, blocks, stream, a, ba, t);
 }
 
 // Top-k step tail (engine/topk.py): row Adam with the norm Jacobian over the [G n, d] dictionary stack
@@ -513,8 +565,10 @@ int sc_topk_tail(float* p, const void* g, float* m, float* v, void* shadow, floa
                  const float* lr, float b1, float b2, float eps, int* step, int gbf16, const float* row_se,
                  int se_rows, float se_scale, float* mse, int* ticket, const void* gbuf, long nbuf,
                  const long* perm, long nperm, const int* ep0, void* gout, long grows, long row_bytes,
-                 hipStream_t stream) {
-  if (d % 256 || d > 1024 || G < 1 || n < 1 || !step || !ticket || !row_se || !mse || se_rows < 1) return 1;
+                 hipStream_t stream, int policy) {
+  if (d % 256 || d > 1024 || G < 1 || n < 1 || !step || !ticket || !row_se || !mse || se_rows < 1 || policy < 0 ||
+      policy > 3)
+    return 1;
   AdamArgs a;
   const int rows = G * n, norm = 1;
   fill_adam(a, 1, &p, &g, &m, &v, &shadow, &norms, &rows, &norm, d, n, lr, b1, b2, eps, 1.f, 1.f, step, 1, 0, 0,
@@ -528,7 +582,7 @@ int sc_topk_tail(float* p, const void* g, float* m, float* v, void* shadow, floa
   t.lG = G;
   t.row_se = row_se; t.se_rows = se_rows; t.se_scale = se_scale; t.mse = mse;
   const long blocks = t.nloss + t.ngather + ((long)G * n + 3) / 4;
-  return launch_tail(d, gbf16, blocks, stream, a, ba, t);
+  return launch_tail(d, gbf16, policy, blocks, stream, a, ba, t);
 }
 
 }  // extern "C"

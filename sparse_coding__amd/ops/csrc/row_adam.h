@@ -42,15 +42,41 @@ __device__ __forceinline__ void shadow_row(const float* P, uint16_t* S, float* n
   }
 }
 
+// Cache policy of the fp32 master / moment streams (p, m, v: touched once per step, so caching them only
+// costs the GEMM operands their place): bit 0 streams the loads, bit 1 the stores (non-temporal).  The
+// gradient loads and the bf16 shadow / row-norm stores keep the default policy: the weight gradient has
+// just written the one, the next step's GEMMs read the others.
+constexpr int POL_NT_LOAD = 1, POL_NT_STORE = 2;
+
+template <bool NT>
+__device__ __forceinline__ float4 ld_f4(const float* p) {
+  if constexpr (NT) {
+    const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+  } else {
+    return *reinterpret_cast<const float4*>(p);
+  }
+}
+
+template <bool NT>
+__device__ __forceinline__ void st_f4(float* p, const float4& v) {
+  if constexpr (NT) {
+    __builtin_nontemporal_store(__builtin_bit_cast(f32x4_t, v), reinterpret_cast<f32x4_t*>(p));
+  } else {
+    *reinterpret_cast<float4*>(p) = v;
+  }
+}
+
 // One dictionary row of the fused Adam, one wave (d = 256 NV): applies the norm Jacobian (norm rows),
 // the Adam update, recomputes the row norm and writes the bf16 shadow (normalised for norm rows).
 // GBF: the gradient arrives in bf16 (the weight-gradient GEMM's bf16 epilogue): 1/7 of the HBM bytes
 // less to read; the moments, the master and the update arithmetic stay fp32.  nsplit > 1: the
 // gradient arrives as split-K partial slabs gstride elements apart (summed here).
-template <int NV, bool GBF = false>
+template <int NV, bool GBF = false, int POL = 0>
 __device__ __forceinline__ void adam_row_core(float* P, const void* G, float* M, float* V, uint16_t* shadow,
                                               float* norms, long row, int norm, int nsplit, long gstride, float lr,
                                               float b1, float b2, float eps, float bc1, float bc2, int lane) {
+  constexpr bool NTL = (POL & POL_NT_LOAD) != 0, NTS = (POL & POL_NT_STORE) != 0;
   const int d = NV * 256;
   const long base = row * d;
   // NV float4 chunks per lane (d == 256 * NV); compile-time so pv/gv stay in VGPRs.
@@ -64,15 +90,15 @@ __device__ __forceinline__ void adam_row_core(float* P, const void* G, float* M,
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int e = (i * 64 + lane) * 4;
-    pv[i] = *reinterpret_cast<const float4*>(P4 + e);
+    pv[i] = ld_f4<NTL>(P4 + e);
     if constexpr (GBF) {
       const ushort4 h = *reinterpret_cast<const ushort4*>(GH + e);
       gv[i] = make_float4(bf2f(h.x), bf2f(h.y), bf2f(h.z), bf2f(h.w));
     } else {
       gv[i] = *reinterpret_cast<const float4*>(G4 + e);
     }
-    mv_[i] = *reinterpret_cast<const float4*>(M + base + e);
-    vv_[i] = *reinterpret_cast<const float4*>(V + base + e);
+    mv_[i] = ld_f4<NTL>(M + base + e);
+    vv_[i] = ld_f4<NTL>(V + base + e);
   }
   if (nsplit > 1) {  // split-K partials of the weight-gradient GEMM (few-model shards)
     for (int sp = 1; sp < nsplit; ++sp) {
@@ -90,11 +116,17 @@ __device__ __forceinline__ void adam_row_core(float* P, const void* G, float* M,
       }
     }
   }
+  // Where a sum of products can be fused into multiply-adds in more than one way, the way is written
+  // out (`a * b + c * d` is fma(a, b, c * d) or fma(c, d, a * b): two roundings of two different
+  // products).  Left to the compiler, the choice moved with the cache policy of the stores -- the
+  // streamed-store builds of d >= 512 fused <w, g> the other way round and wrote other bits -- so the
+  // forms below are the ones every build took before there was a policy.
   float ss = 0.f, dot = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    ss += pv[i].x * pv[i].x + pv[i].y * pv[i].y + pv[i].z * pv[i].z + pv[i].w * pv[i].w;
-    dot += pv[i].x * gv[i].x + pv[i].y * gv[i].y + pv[i].z * gv[i].z + pv[i].w * gv[i].w;
+    const float4 p = pv[i], g = gv[i];
+    ss += __fmaf_rn(p.w, p.w, __fmaf_rn(p.z, p.z, __fmaf_rn(p.x, p.x, p.y * p.y)));
+    dot += __fmaf_rn(p.w, g.w, __fmaf_rn(p.z, g.z, __fmaf_rn(p.x, g.x, p.y * g.y)));
   }
   float gs = 1.f, ws = 0.f;
   if (norm) {
@@ -124,15 +156,15 @@ __device__ __forceinline__ void adam_row_core(float* P, const void* G, float* M,
     float* vvv = reinterpret_cast<float*>(&vv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float gk = gg[k] * gs - pp[k] * ws;
-      mm[k] = b1 * mm[k] + omb1 * gk;
-      vvv[k] = b2 * vvv[k] + omb2 * gk * gk;
+      const float gk = __fmaf_rn(gg[k], gs, -(pp[k] * ws));
+      mm[k] = __fmaf_rn(b1, mm[k], omb1 * gk);
+      vvv[k] = __fmaf_rn(b2, vvv[k], omb2 * gk * gk);
       pp[k] -= step * mm[k] / (sqrtf(vvv[k] * rbc2) + eps);
       ss2 += pp[k] * pp[k];
     }
-    *reinterpret_cast<float4*>(M + base + e) = mv;
-    *reinterpret_cast<float4*>(V + base + e) = vv;
-    *reinterpret_cast<float4*>(P + base + e) = pv[i];
+    st_f4<NTS>(M + base + e, mv);
+    st_f4<NTS>(V + base + e, vv);
+    st_f4<NTS>(P + base + e, pv[i]);
   }
   float sc = 1.f;
   if (norm) {
