@@ -777,14 +777,19 @@ class FusedSAEEnsemble:
         self._host_step()
         return self.out
 
+    def _encode_only(self, x, cnt_part=None):
+        """The grouped encoder launch alone on one prepared batch ``x``: overwrites the scratch ``c`` /
+        ``cmask`` / ``enc_part`` (``_forward_only`` and ``feature_stats``)."""
+        gemm_ops.encode_relu(x, self.enc_shadow, self.params[self._bkey], self.c, self.enc_part, cnt_part,
+                             self.nactive, mask_out=self.cmask, act=self.act,
+                             ascale=self.s2 if self.kind == "threshold" else None, live_host=self._live)
+
     def _forward_only(self, x, target=None, cnt_part=None):
         """Codes and residual of one prepared batch ``x`` without gradients (``evaluate`` and the pool
         scoring of ``resample_dead``): overwrites the scratch buffers ``c`` / ``r`` / ``cmask`` and the
         epilogue partials ``enc_part`` / ``dec_part``; fire counts go to ``cnt_part`` when given.
         ``target``: the rows to reconstruct when they are not ``x`` (threshold SAEs)."""
-        gemm_ops.encode_relu(x, self.enc_shadow, self.params[self._bkey], self.c, self.enc_part, cnt_part,
-                             self.nactive, mask_out=self.cmask, act=self.act,
-                             ascale=self.s2 if self.kind == "threshold" else None, live_host=self._live)
+        self._encode_only(x, cnt_part)
         gemm_ops.decode_residual(self.c, self.dec_shadow, x if target is None else target, self.r, self.dec_part)
 
     @torch.no_grad()
@@ -893,6 +898,73 @@ class FusedSAEEnsemble:
         self.rows_seen = 0
         self._bsq_dirty = True
         return cnt
+
+    def _stats_unsupported(self) -> Optional[str]:
+        if self.kind == "threshold":
+            return "threshold SAEs: the codes are not a ReLU of the encoder's pre-activation"
+        if self.kind == "reverse":
+            return "reverse SAEs: the bias-subtracted codes are not a ReLU of the encoder's pre-activation"
+        if self.learned_center:
+            return "learned centering is not covered"
+        return None
+
+    @torch.no_grad()
+    def feature_stats(self, rows: torch.Tensor, *, topk: int = 0, row_offset: int = 0, state=None):
+        """Per-feature activation statistics of every model on ``rows`` [N, d] (N a positive multiple of
+        the batch size): a ``engine.feature_stats.FeatureStats`` with the fire count, the sums of c ..
+        c^4, the largest code and -- ``topk`` in 1..32 -- the ``topk`` largest positive codes of every
+        feature with their row indices (``row_offset`` + position in ``rows``).  Never synchronises.
+
+        Per batch: the encoder launch alone (as ``evaluate``, the scratch buffers ``c`` / ``cmask`` /
+        ``enc_part`` are overwritten; no decoder), then ``col_moments`` and ``col_topk`` over the bf16
+        codes (``csrc/feature_stats.hip``); the slab partials are summed into fp64 accumulators on the
+        device.  ``state``: the result of an earlier call to continue (with ``row_offset`` the rows
+        already seen) -- chunk by chunk gives the bits of one call on the whole pool.  Tied models
+        with a fixed affine centering: the codes of the centred rows, the space the model is trained in
+        (``LearnedDict.encode`` does not centre: ``calc_moments_streaming`` wants ``ld.center(rows)``
+        there).  Masked ensembles: features at or past ``dict_size[g]`` read all zeros and rows of -1.  Parameters,
+        moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and captured graphs are
+        left as they are."""
+        from ..ops import feature_stats as fs_ops
+        from . import feature_stats as fs
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"feature_stats: {why}")
+        B, G, n, d = self.batch_size, self.n_models, self.n, self.d
+        if rows.dim() != 2 or rows.shape[1] != d:
+            raise ValueError(f"rows must be [N, {d}], got {tuple(rows.shape)}")
+        N = rows.shape[0]
+        if N <= 0 or N % B:
+            raise ValueError(f"feature_stats needs a positive multiple of the batch size ({B}) rows, got {N}")
+        topk, row_offset = fs.check_request(topk, row_offset, state, G, n)
+        dev = self.device
+        part = getattr(self, "_stats_part", None)
+        if part is None:
+            part = self._stats_part = torch.empty(G, fs_ops.moment_slabs(G, B, n), fs_ops.N_STATS, n, device=dev)
+        tv = tr = None
+        if state is None:
+            acc = torch.zeros(G, 5, n, device=dev, dtype=torch.float64)  # count, sum c .. sum c^4
+            mx = torch.full((G, n), float("-inf"), device=dev)
+            if topk:
+                tv, tr = fs.empty_topk(G, n, topk, dev)
+            seen = 0
+        else:
+            acc = torch.cat([state.count.to(dev, torch.float64).unsqueeze(1), state.sums.to(dev)], dim=1)
+            mx = state.max.to(dev, copy=True)
+            if topk:
+                tv = state.top_vals.to(dev, copy=True).contiguous()
+                tr = state.top_rows.to(dev, copy=True).contiguous()
+            seen = int(state.n_rows)
+        pool = self._x_bf16(rows)
+        for i in range(0, N, B):
+            self._encode_only(self.prepare(pool[i:i + B]))
+            fs_ops.col_moments(self.c, part)
+            if topk:
+                fs_ops.col_topk(self.c, tv, tr, row_offset + i)
+            acc += part[:, :, :5].sum(1, dtype=torch.float64)
+            mx = torch.maximum(mx, part[:, :, 5].amax(1))
+        return fs.FeatureStats(seen + N, acc[:, 0].round().to(torch.int64), acc[:, 1:].contiguous(), mx, tv, tr)
 
     def feature_frequency(self) -> torch.Tensor:
         """Per-feature firing frequency [G, n] = feature_counts / rows_seen.  The counts are SAMPLED:

@@ -317,6 +317,37 @@ class EnsembleTrainer:
         cnt = rs.resample_stacked(impl.params, m, v, rows, kind, live=live, **kw)
         return [int(c) for c in cnt.cpu()]
 
+    # ------------------------------------------------------------------ per-feature statistics
+    def feature_stats(self, rows: torch.Tensor, **kw):
+        """Per-feature activation statistics of every model on ``rows`` [N, d]: an
+        ``engine.feature_stats.FeatureStats`` (keywords ``topk``, ``row_offset``, ``state``).
+
+        The fused SAE engine runs ``FusedSAEEnsemble.feature_stats`` (N a multiple of its batch size;
+        under ensemble sharding each rank gets the statistics of its own models on the rows it is given,
+        N a multiple of the engine's global batch).  The analytic and eager engines with an untied / tied
+        SAE signature run the fp64 oracle on their fp32 torch codes, ``batch_size`` rows at a time.
+        Data-parallel trainers and every other kind raise ``NotImplementedError``."""
+        from . import feature_stats as fs
+
+        if self.dp is not None:
+            raise NotImplementedError("feature_stats: data-parallel replicas (parallel='dp'/'zero1') hold the same "
+                                      "models on different rows; collect the statistics on one rank's engine")
+        if self.kind == "fused-sae":
+            return self.impl.feature_stats(rows.to(self.device), **kw)
+        kind = analytic._KINDS.get(self.sig)
+        if self.kind not in ("analytic", "eager") or kind is None:
+            raise NotImplementedError(f"feature_stats: no code path for the {self.kind} engine with "
+                                      f"{getattr(self.sig, '__name__', self.sig)}")
+        impl = self.impl
+        d = impl.params["encoder"].shape[-1]
+        if rows.dim() != 2 or rows.shape[1] != d or rows.shape[0] < 1:
+            raise ValueError(f"rows must be [N, {d}] with N >= 1, got {tuple(rows.shape)}")
+        buffers = getattr(impl, "buffers", {})
+        with torch.no_grad():
+            codes = (fs.stacked_codes(impl.params, buffers, kind, rows[i:i + self.batch_size])
+                     for i in range(0, rows.shape[0], self.batch_size))
+            return fs.feature_stats_reference(codes, **kw)
+
     # ------------------------------------------------------------------ export / state
     def hyperparams(self, ensemble_hyperparams: Sequence[str] = (), buffer_hyperparams: Sequence[str] = ("l1_alpha",),
                     local: bool = False) -> List[dict]:

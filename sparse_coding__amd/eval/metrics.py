@@ -215,6 +215,20 @@ def calc_moments_streaming(learned_dict: LearnedDict, activations: torch.Tensor,
     return times_active, f(mean), f(var), f(skew), f(kurt), f(m4)
 
 
+def ensemble_moments_streaming(engine_or_trainer, activations: torch.Tensor):
+    """``calc_moments_streaming`` for every model of an ensemble in one pass: ``engine_or_trainer`` is a
+    ``FusedSAEEnsemble`` or an ``EnsembleTrainer`` (anything with ``feature_stats`` and ``batch_size``).
+    The activations are trimmed to a multiple of the batch size.  Returns (rows used, one
+    (times_active, mean, var, skew, kurtosis, m4) tuple per model)."""
+    # (a sharded trainer's engine works on the gathered global batch)
+    B = int(getattr(getattr(engine_or_trainer, "impl", None), "batch_size", engine_or_trainer.batch_size))
+    N =activations.shape[0] - activations.shape[0] % B
+    if N == 0:
+        raise ValueError(f"need at least {B} rows")
+    stats = engine_or_trainer.feature_stats(activations[:N])
+    return N, [stats.per_model(g) for g in range(stats.count.shape[0])]
+
+
 def ridge_regression_auroc(activations: torch.Tensor, labels: torch.Tensor, **kwargs) -> float:
     """Linear-probe AUROC (reference :252-258)."""
     from sklearn import metrics as skm

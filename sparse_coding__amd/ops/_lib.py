@@ -56,6 +56,8 @@ def signatures():
         "sc_resample_rows": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_int, c_int, c_int,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+        "sc_col_moments": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+        "sc_col_topk": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
