@@ -125,6 +125,32 @@ def _bf16(t, name):
     _need(t.is_contiguous(), f"{name} must be contiguous")
 
 
+# The kernel addresses every operand through a buffer resource of 2^31 - 1 records and forms its
+# byte offsets in 32 bits (csrc/gemm_tiles.h: make_rsrc, piece_offsets): one model's slice of an
+# operand must end below that.
+MAX_OPERAND_SPAN = 2 ** 31 - 1
+
+
+def operand_span_bytes(rows: int, K: int, ld: int, kmajor: bool) -> int:
+    """Bytes from an operand's per-model base to the end of its last bf16 element: ``rows`` x ``K``
+    stored K-major ([rows][ld]) or row-major in K ([K][ld])."""
+    last = (rows - 1) * ld + K if kmajor else (K - 1) * ld + rows
+    return 2 * last
+
+
+def check_operand_spans(layout: int, M: int, N: int, K1: int, K2: int, a_lds, b_lds):
+    """Raise ValueError when a K segment of A (``a_lds``: its leading dimensions) or B reaches
+    ``MAX_OPERAND_SPAN`` bytes within one model."""
+    for name, rows, kmajor, lds in (("A", M, bool(layout & 1), a_lds), ("B", N, bool(layout & 2), b_lds)):
+        for seg, K in enumerate((K1, K2)):
+            if K == 0:
+                continue
+            for ld in lds[seg::2]:
+                span = operand_span_bytes(rows, K, int(ld), kmajor)
+                _need(span < MAX_OPERAND_SPAN, f"operand {name} (segment {seg}: {rows} x {K}, ld {ld}) spans {span} bytes "
+                                               f"per model; the kernel addresses less than {MAX_OPERAND_SPAN}")
+
+
 def _launch(epi, layout, M, N, K1, K2, G, a_ops, b_ops, outs, alphas, ldc, sc, *,
             bias=None, sbias=0, nactive=None, aux=None, ldaux=0, saux=0, part=None,
             colpart=None, l1=None, l1_add_scale=0.0, dotpart=None, dc_tied=False, cfg=None,
@@ -132,6 +158,7 @@ def _launch(epi, layout, M, N, K1, K2, G, a_ops, b_ops, outs, alphas, ldc, sc, *
             nact_k=None, nact_host=None):
     _need(M % TILE_M == 0 and N % TILE_N == 0, f"M={M}, N={N} must be multiples of 128")
     _need(K1 % TILE_K == 0 and K2 % TILE_K == 0, f"K={K1}+{K2} must be multiples of 64")
+    check_operand_spans(layout, M, N, K1, K2, [o.ld for o in a_ops], [o.ld for o in b_ops])
     if cfg is None:
         cfg = _CFG_OVERRIDE if _CFG_OVERRIDE is not None else _CFG_LAYOUT.get((epi, layout), _CFG_DEFAULT[epi])
         if _CFG_OVERRIDE is None and (((cfg & 3) and not shape_fits(cfg, M, N))
