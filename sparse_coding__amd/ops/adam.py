@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, store_policy
 
 
 # Launch policy of the row-Adam kernels (csrc/adam.hip, csrc/row_adam.h): bit 0 streams the fp32 p / m / v
@@ -41,6 +41,12 @@ def set_policy(pol: int):
     if not 0 <= int(pol) <= 3:
         raise ValueError(f"policy must be in 0..3 (got {pol})")
     _POLICY = int(pol)
+
+
+def _launch_policy() -> int:
+    """The policy argument of the row-Adam entry points: the launch policy in bits 0-1, the write-through
+    bits of ``ops/store_policy.py`` above them."""
+    return _POLICY | store_policy.tail_bits()
 
 
 def _vp(seq):
@@ -121,7 +127,7 @@ def adam_rows(sets, lr, step, b1=0.9, b2=0.999, eps=1e-8, rows_per_model=None, s
         _vp([s.get("shadow") for s in sets]), _vp([s.get("norms") for s in sets]),
         rows, norm, d, rpm, _lib.ptr(lr), b1, b2, eps, bc1, bc2,
         _lib.ptr(step_dev), int(nsplit), int(gstride), int(row0), _lib.stream_handle(), _lib.ptr(live),
-        int(gbf16), _POLICY,
+        int(gbf16), _launch_policy(),
     )
     _lib.check(rc, "sc_adam_rows")
 
@@ -208,7 +214,7 @@ def step_tail(sets, lr, b1, b2, eps, step_dev, bias, bias_m, bias_v, colpart, en
         gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes,
         int(nsplit), int(gstride), _lib.ptr(live), int(cnt_tm), int(row0 or 0),
         C.cast((C.c_int * len(live_host))(*[int(v) for v in live_host]), C.c_void_p)
-        if (live_host is not None and live is not None) else None, _lib.stream_handle(), _POLICY,
+        if (live_host is not None and live is not None) else None, _lib.stream_handle(), _launch_policy(),
     )
     _lib.check(rc, "sc_step_tail")
 
@@ -239,7 +245,7 @@ def topk_tail(p, g, m, v, shadow, norms, lr, b1, b2, eps, step_dev, row_se, mse,
         _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), _lib.ptr(shadow), _lib.ptr(norms), G, n, d,
         _lib.ptr(lr), b1, b2, eps, _lib.ptr(step_dev), int(gbf16), _lib.ptr(row_se), row_se.shape[1],
         float(se_scale), _lib.ptr(mse), _lib.ptr(ticket), gbuf, nbuf, perm, nperm, ep0, gout, grows, row_bytes,
-        _lib.stream_handle(), _POLICY,
+        _lib.stream_handle(), _launch_policy(),
     )
     _lib.check(rc, "sc_topk_tail")
 

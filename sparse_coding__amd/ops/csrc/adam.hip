@@ -46,7 +46,8 @@ struct AdamArgs {
 
 // The row-Adam kernels are templated on a launch policy POL (one integer argument of sc_step_tail /
 // sc_topk_tail / sc_adam_rows; ops/adam.py reads it once from SC_TAIL_POLICY): POL_NT_LOAD |
-// POL_NT_STORE (row_adam.h).  (An XCD-affine, model-major order of the tail's row blocks, so that the
+// POL_NT_STORE (row_adam.h).  The step tails also take POL_WT_PMV / POL_WT_AUX (bits 2 and 3, from
+// ops/store_policy.py): stores written through the L2; sc_adam_rows accepts and ignores them.  (An XCD-affine, model-major order of the tail's row blocks, so that the
 // XCD that reads model g's shadows next step writes them, lost on the headline, 0.2865 vs 0.2820 ms
 // alone and nothing on top of the streamed accesses: scripts/lab/tail_cache_r8.patch,
 // profiles/r8/tail_cache/README.md.)
@@ -274,6 +275,7 @@ struct TailArgs {
   // next-step gather (ngather blocks; 0 = none): out[r] = buf[perm[(t + 1 - ep0) * rows + r]]
   const u32x4_t* gbuf; long nbuf; const long* perm; long nperm; const int* ep0; u32x4_t* gout; long grows;
   int row_vec;
+  int gwt;                    // the gather's stores written through the L2 (POL_WT_AUX, span permitting)
   int nloss, nbias, ngather;  // block counts of the roles
   // masked ensembles: the row-Adam blocks cover only live rows (lcomp: live-row prefix lpre[g] over
   // the models, the same for every set; compact row rc of set s -> row g n + rc - lpre[g] of model g)
@@ -327,8 +329,9 @@ __device__ __forceinline__ void tail_gather(const TailArgs& t, int step, long r)
   long src = (jj >= 0 && jj < t.nperm) ? t.perm[jj] : 0;
   src = (src >= 0 && src < t.nbuf) ? src : 0;
   const u32x4_t* sp = t.gbuf + src * t.row_vec;
-  u32x4_t* op = t.gout + r * t.row_vec;
-  for (int v = lane; v < t.row_vec; v += 64) op[v] = sp[v];
+  const rsrc_t grs = store_rsrc(t.gout);
+  const bool wt = t.gwt != 0;
+  for (int v = lane; v < t.row_vec; v += 64) st_out(wt, grs, t.gout, (r * t.row_vec + v) * 16, sp[v]);
 }
 
 template <int NV, bool GBF, int POL>
@@ -402,6 +405,16 @@ static long fill_adam(AdamArgs& a, int nset, float* const* p, const void* const*
   return total;
 }
 
+// The written-through stores address an array with 32-bit byte offsets (common.h store_rsrc).
+static bool wt_span_ok(long bytes) { return bytes < 0x7FFFFFFFl; }
+
+// The kernel policy of a step-tail launch from the entry point's policy argument: the write-through bits
+// are kept only where the arrays they address are small enough (one parameter set; the gathered batch).
+static int tail_policy(int policy, long set_rows, int d, TailArgs& t, long gather_bytes) {
+  t.gwt = (policy & POL_WT_AUX) && wt_span_ok(gather_bytes);
+  return wt_span_ok(set_rows * d * 4) ? policy : (policy & 3);
+}
+
 // Fills the next-batch gather of a step tail (gbuf == nullptr: none); false if the rows cannot be
 // copied as 16-byte vectors.
 static bool fill_gather(TailArgs& t, const void* gbuf, long nbuf, const long* perm, long nperm, const int* ep0,
@@ -421,6 +434,9 @@ static void launch_tail_pol(int pol, long blocks, hipStream_t stream, const Adam
   case P: hipLaunchKernelGGL((step_tail_kernel<NV, GBF, P>), dim3(blocks), dim3(256), 0, stream, a, ba, t); break;
   switch (pol) {
     SC_TAIL_POL(0) SC_TAIL_POL(1) SC_TAIL_POL(2) SC_TAIL_POL(3)
+    SC_TAIL_POL(4) SC_TAIL_POL(5) SC_TAIL_POL(6) SC_TAIL_POL(7)
+    SC_TAIL_POL(8) SC_TAIL_POL(9) SC_TAIL_POL(10) SC_TAIL_POL(11)
+    SC_TAIL_POL(12) SC_TAIL_POL(13) SC_TAIL_POL(14) SC_TAIL_POL(15)
   }
 #undef SC_TAIL_POL
 }
@@ -461,12 +477,12 @@ int sc_adam_rows(int nset, float* const* p, const void* const* g, float* const* 
                  int rows_per_model, const float* lr, float b1, float b2, float eps, float bc1,
                  float bc2, const int* step, int nsplit, long gstride, long row0, hipStream_t stream,
                  const int* live, int gbf16, int policy) {
-  if (d % 256 || d > 4096 || nset < 1 || nset > 2 || nsplit < 1 || policy < 0 || policy > 3) return 1;
+  if (d % 256 || d > 4096 || nset < 1 || nset > 2 || nsplit < 1 || policy < 0 || policy > 15) return 1;
   AdamArgs a;
   const long total = fill_adam(a, nset, p, g, m, v, shadow, norms, rows, norm, d, rows_per_model, lr, b1, b2, eps,
                                bc1, bc2, step, nsplit, gstride, row0, live);
   const long blocks = (total + 3) / 4;
-  const int pol = policy;
+  const int pol = policy & 3;  // (the write-through bits are the step tails')
   // gradients: plain loads only, whatever the policy (the NT knob on them A/B'd slower, profiles/)
 #define SC_ADAM(NVV)                                                        \
   case NVV:                                                                 \
@@ -519,7 +535,7 @@ int sc_step_tail(int nset, float* const* p, const void* const* g, float* const* 
                  const int* ep0, void* gout, long grows, long row_bytes, int nsplit, long gstride,
                  const int* live, int cnt_tm, long row0, const int* live_h, hipStream_t stream, int policy) {
   if (d % 256 || d > 4096 || nset < 1 || nset > 2 || n % 32 || !step || !ticket || !bsq || nsplit < 1 ||
-      policy < 0 || policy > 3)
+      policy < 0 || policy > 15)
     return 1;
   AdamArgs a;
   // live: masked ensembles (may be null); row0: the sets are rows [row0, row0 + rows) of the
@@ -554,7 +570,8 @@ int sc_step_tail(int nset, float* const* p, const void* const* g, float* const* 
     }
   }
   const long blocks = t.nloss + t.nbias + t.ngather + (arows + 3) / 4;
-  return launch_tail(d, gbf16, policy, blocks, stream, a, ba, t);
+  const int pol = tail_policy(policy, std::max(rows[0], nset > 1 ? rows[1] : 0), d, t, t.grows * row_bytes);
+  return launch_tail(d, gbf16, pol, blocks, stream, a, ba, t);
 }
 
 // Top-k step tail (engine/topk.py): row Adam with the norm Jacobian over the [G n, d] dictionary stack
@@ -567,7 +584,7 @@ int sc_topk_tail(float* p, const void* g, float* m, float* v, void* shadow, floa
                  const long* perm, long nperm, const int* ep0, void* gout, long grows, long row_bytes,
                  hipStream_t stream, int policy) {
   if (d % 256 || d > 1024 || G < 1 || n < 1 || !step || !ticket || !row_se || !mse || se_rows < 1 || policy < 0 ||
-      policy > 3)
+      policy > 15)
     return 1;
   AdamArgs a;
   const int rows = G * n, norm = 1;
@@ -582,7 +599,7 @@ int sc_topk_tail(float* p, const void* g, float* m, float* v, void* shadow, floa
   t.lG = G;
   t.row_se = row_se; t.se_rows = se_rows; t.se_scale = se_scale; t.mse = mse;
   const long blocks = t.nloss + t.ngather + ((long)G * n + 3) / 4;
-  return launch_tail(d, gbf16, policy, blocks, stream, a, ba, t);
+  return launch_tail(d, gbf16, tail_policy(policy, rows, d, t, t.grows * row_bytes), blocks, stream, a, ba, t);
 }
 
 }  // extern "C"

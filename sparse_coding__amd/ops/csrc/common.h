@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace scamd {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -13,6 +15,53 @@ typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 typedef short i16x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+
+// ------------------------------------------------------------------ global-store cache policy
+// The eight XCD L2s are write-back and not coherent with each other, so the release at the end of a
+// kernel writes every dirty line back before the dependent kernel starts.  An `sc1` store is written
+// through: its bytes leave the L2 while the kernel is still running (MI355X_MICROARCH.md, "stores of
+// each flavour").  `nt` alone only changes retention.  The values are the `aux` operand of the raw
+// buffer stores, which is the only compiler-visible 16-byte store that takes `sc1` (an inline-asm
+// store would not be counted in hipcc's vmcnt bookkeeping).  Cache hints only: every policy writes
+// the same bits.
+enum { ST_PLAIN = 0, ST_NT = 2, ST_SC1 = 16, ST_NT_SC1 = 18 };
+
+// Buffer resource over [base, base + 2^31 - 1) for st_pol's written-through forms: byte offsets are
+// 32-bit, so the host keeps write-through off for any output that spans more (ops/store_policy.py).
+// `base` must be wave-uniform; the readfirstlanes make that provable (no waterfall loops).
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+__device__ __forceinline__ rsrc_t store_rsrc(const void* base) {
+  const uint64_t a = reinterpret_cast<uint64_t>(base);
+  const uint64_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+  const uint64_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((hi << 32) | lo), 0, 0x7FFFFFFF, 0x00020000);
+}
+
+// One whole 16-byte or 8-byte store of `v` at base + off under policy POL.  The plain and `nt` forms
+// address base + off in 64 bits (any span); the `sc1` forms go through `rs` = store_rsrc(base).
+template <int POL, class V>
+__device__ __forceinline__ void st_pol(const rsrc_t& rs, void* base, long off, const V& v) {
+  static_assert(sizeof(V) == 16 || sizeof(V) == 8, "whole 16-byte or 8-byte pieces only");
+  using U = typename std::conditional<sizeof(V) == 16, u32x4_t, u32x2_t>::type;
+  const U u = __builtin_bit_cast(U, v);
+  if constexpr (POL == ST_PLAIN) {
+    *reinterpret_cast<U*>(reinterpret_cast<char*>(base) + off) = u;
+  } else if constexpr (POL == ST_NT) {
+    __builtin_nontemporal_store(u, reinterpret_cast<U*>(reinterpret_cast<char*>(base) + off));
+  } else if constexpr (sizeof(V) == 16) {
+    __builtin_amdgcn_raw_buffer_store_b128(u, rs, (int)off, 0, POL);
+  } else {
+    __builtin_amdgcn_raw_buffer_store_b64(u, rs, (int)off, 0, POL);
+  }
+}
+
+// Run-time choice between the plain and the written-through store (wave-uniform `wt`).
+template <class V>
+__device__ __forceinline__ void st_out(bool wt, const rsrc_t& rs, void* base, long off, const V& v) {
+  if (wt) st_pol<ST_SC1>(rs, base, off, v);
+  else st_pol<ST_PLAIN>(rs, base, off, v);
+}
 
 #define SC_LDS(T, p) ((__attribute__((address_space(3))) T*)(p))
 

@@ -112,6 +112,9 @@ struct GemmParams {
   int tpre[17];
   int tl[16];
   FDiv fl[16];
+  // --- output-tile and activity-mask stores written through the L2 (common.h st_out); the caller
+  // leaves it 0 when a model's output spans 2^31 - 1 bytes or more
+  int store_wt;
 };
 
 // LDS image of a K-major tile [128 rows][BKT k] bf16.

@@ -47,6 +47,13 @@ __device__ __forceinline__ void shadow_row(const float* P, uint16_t* S, float* n
 // gradient loads and the bf16 shadow / row-norm stores keep the default policy: the weight gradient has
 // just written the one, the next step's GEMMs read the others.
 constexpr int POL_NT_LOAD = 1, POL_NT_STORE = 2;
+// Bits 2 and 3 (ops/store_policy.py; step tails only): the p / m / v stores, and the bf16 shadow / row-norm
+// stores, written through the L2 (`sc1`, common.h st_pol) so that the end of the launch does not have to
+// write them back; POL_WT_PMV on top of POL_NT_STORE gives `nt sc1`.  Compile-time like bits 0 and 1, and
+// the code without them is left exactly as it was: a run-time branch around the stores changed how the
+// compiler fused the update's multiply-adds (other bits, see below).  The written-through forms address a
+// whole parameter set with 32-bit byte offsets; the launchers drop the bits for larger sets.
+constexpr int POL_WT_PMV = 4, POL_WT_AUX = 8;
 
 template <bool NT>
 __device__ __forceinline__ float4 ld_f4(const float* p) {
@@ -77,6 +84,8 @@ __device__ __forceinline__ void adam_row_core(float* P, const void* G, float* M,
                                               float* norms, long row, int norm, int nsplit, long gstride, float lr,
                                               float b1, float b2, float eps, float bc1, float bc2, int lane) {
   constexpr bool NTL = (POL & POL_NT_LOAD) != 0, NTS = (POL & POL_NT_STORE) != 0;
+  constexpr bool WTP = (POL & POL_WT_PMV) != 0, WTA = (POL & POL_WT_AUX) != 0;
+  constexpr int PMV_POL = (NTS ? ST_NT : ST_PLAIN) | ST_SC1;  // the written-through p / m / v store
   const int d = NV * 256;
   const long base = row * d;
   // NV float4 chunks per lane (d == 256 * NV); compile-time so pv/gv stay in VGPRs.
@@ -160,18 +169,40 @@ __device__ __forceinline__ void adam_row_core(float* P, const void* G, float* M,
       mm[k] = __fmaf_rn(b1, mm[k], omb1 * gk);
       vvv[k] = __fmaf_rn(b2, vvv[k], omb2 * gk * gk);
       pp[k] -= step * mm[k] / (sqrtf(vvv[k] * rbc2) + eps);
-      ss2 += pp[k] * pp[k];
     }
-    st_f4<NTS>(M + base + e, mv);
-    st_f4<NTS>(V + base + e, vv);
-    st_f4<NTS>(P + base + e, pv[i]);
+    if constexpr (WTP) {
+      st_pol<PMV_POL>(store_rsrc(M), M, (base + e) * 4, mv);
+      st_pol<PMV_POL>(store_rsrc(V), V, (base + e) * 4, vv);
+      st_pol<PMV_POL>(store_rsrc(P), P, (base + e) * 4, pv[i]);
+    } else {
+      st_f4<NTS>(M + base + e, mv);
+      st_f4<NTS>(V + base + e, vv);
+      st_f4<NTS>(P + base + e, pv[i]);
+    }
+  }
+  // |w_new|^2, written out like the sums above.  Left as `ss2 += pp[k] * pp[k]` in the update loop, the
+  // builds with written-through shadow stores multiplied and added where every build before them had
+  // fused.  The form is the one read from those earlier builds' assembly, at every row width: the first
+  // two squares as one fused pair, multiply-adds up to the last two, which are rounded and then added.
+  {
+    const float* w = reinterpret_cast<const float*>(pv);
+    ss2 = __fmaf_rn(w[0], w[0], __fmul_rn(w[1], w[1]));
+#pragma unroll
+    for (int j = 2; j < 4 * NV - 2; ++j) ss2 = __fmaf_rn(w[j], w[j], ss2);
+    ss2 = __fadd_rn(ss2, __fmul_rn(w[4 * NV - 2], w[4 * NV - 2]));
+    ss2 = __fadd_rn(ss2, __fmul_rn(w[4 * NV - 1], w[4 * NV - 1]));
   }
   float sc = 1.f;
   if (norm) {
     ss2 = wave_sum(ss2);
     const float nrm = fmaxf(sqrtf(ss2), 1e-8f);
     sc = 1.f / nrm;
-    if (norms && lane == 0) norms[row] = nrm;
+    if constexpr (WTA) {
+      // (a 4-byte value: the relaxed agent-scope store is the compiler's `global_store_dword ... sc1`)
+      if (norms && lane == 0) __hip_atomic_store(norms + row, nrm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      if (norms && lane == 0) norms[row] = nrm;
+    }
   }
   if (shadow) {
 #pragma unroll
@@ -182,7 +213,8 @@ __device__ __forceinline__ void adam_row_core(float* P, const void* G, float* M,
       h.y = f2bf(pv[i].y * sc);
       h.z = f2bf(pv[i].z * sc);
       h.w = f2bf(pv[i].w * sc);
-      *reinterpret_cast<ushort4*>(shadow + base + e) = h;
+      if constexpr (WTA) st_pol<ST_SC1>(store_rsrc(shadow), shadow, (base + e) * 2, h);
+      else *reinterpret_cast<ushort4*>(shadow + base + e) = h;
     }
   }
 }

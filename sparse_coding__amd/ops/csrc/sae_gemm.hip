@@ -34,6 +34,7 @@ int sc_gemm_shape(int M, int N, int G, int nprob) {
 // cfg bits 0-1: 0 = automatic shape, 1 = 128x128, 2 = 256x128, 3 = 256x256;
 // bits 2-3: K pipeline (0: BK64 x 2-stage LDS ring, 1: BK32 x 4 (128x128 blocks: BK64 x 3),
 // 2: BK32 x 2, 3: BK32 x 3); bit 4: 128x128 on the BK32 rings with the software-pipelined K loop.
+// store_wt != 0: the output tiles and activity-mask words are written through the L2 (common.h st_out).
 int sc_gemm(int epi, int layout, int nprob, int M, int N, int K1, int K2, int G,
             const ScOperand* a /* [nprob][2] */, const ScOperand* b /* [nprob][2] */,
             void* const* c /* [nprob] */, const float* alpha /* [nprob] */, long ldc, long sc,
@@ -41,7 +42,7 @@ int sc_gemm(int epi, int layout, int nprob, int M, int N, int K1, int K2, int G,
             long saux, float* part, float* colpart, const float* l1, float l1_add_scale,
             float* dotpart, int dc_tied, int cfg, int ksplit, long split_stride, void* cmask, int act, const float* ascale,
             void* cmask2, float* rcol, const int* nact_m, const int* nact_k, const int* nact_host,
-            hipStream_t stream) {
+            hipStream_t stream, int store_wt) {
   if (M % PT || N % PT || K1 % 64 || K2 % 64 || nprob < 1 || nprob > 2 || G < 1) return 1;
   if ((epi == EPI_DC_MASK || epi == EPI_DC_ACT) && !cmask) return 4;
   if (epi == EPI_DC_ACT && (!aux || !colpart || !l1)) return 4;
@@ -68,6 +69,9 @@ int sc_gemm(int epi, int layout, int nprob, int M, int N, int K1, int K2, int G,
   p.act = act; p.ascale = ascale;
   p.cmask2 = reinterpret_cast<uint64_t*>(cmask2); p.rcol = rcol;
   p.nact_m = nact_m; p.nact_k = nact_k;
+  // written-through stores address one model's output with 32-bit byte offsets: plain stores beyond that
+  const long esz = (epi == EPI_F32 || epi == EPI_ROWMAX) ? 4 : 2;
+  p.store_wt = store_wt != 0 && ((long)(M - 1) * ldc + N) * esz < 0x7FFFFFFFl;
   // masked launches with host copies of the live sizes launch only their live tiles
   p.want_comp = nact_host != nullptr && G <= 16;
   p.ncomp = 0;

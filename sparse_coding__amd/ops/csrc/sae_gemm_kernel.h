@@ -149,7 +149,7 @@ constexpr int stage_off() { return ((2 * S::WGM * S::BN + 2 * S::NW) * 4 + STAGE
 template <class S>
 constexpr int stage_bytes() { return stage_off<S>() + S::NW * stage_wave<S>(); }
 
-template <class S, int EPI, bool AUX_EARLY, bool STAGE = false, bool FSTAGE = false>
+template <class S, int EPI, bool AUX_EARLY, bool STAGE = false, bool FSTAGE = false, bool WTC = true>
 __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)[S::WI][S::WJ],
                                              const uint2 (&auxv)[S::WI][S::WJ], const f32x4_t (&biasv)[S::WJ],
                                              const uint64_t (&mkv)[S::WI / 4],
@@ -168,26 +168,44 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
   static_assert(!STAGE || ((WI == 4 || WI == 8) && WJ == 4 && 2 * S::WGM * BN + 2 * NW <= stage_off<S>() / 4),
                 "stage layout");
   char* stage = reinterpret_cast<char*>(red) + stage_off<S>() + wid * stage_wave<S>();
+  // Output-tile stores go through st_out (common.h): plain, or written through the L2 (`sc1`) when the
+  // launch asks for it (GemmParams::store_wt; block-uniform), so that the release at the end of the
+  // kernel finds the tile already out of the L2.  The written-through form addresses this model's
+  // output through a buffer resource with 32-bit byte offsets (the host keeps it off for larger spans).
+  constexpr int ESZ = (EPI == EPI_F32 || EPI == EPI_ROWMAX) ? 4 : 2;
+  const bool wt = WTC && p.store_wt != 0;  // (WTC false: an instantiation that keeps plain stores, see gemm_block)
+  char* const Cg = reinterpret_cast<char*>(cptr) + (long)g * p.sc * ESZ;  // this model's output
+  const rsrc_t crs = store_rsrc(Cg);
   // one 4-wide bf16 output fragment (rows rowb + 16 i, columns colb + 16 j .. +3)
   auto put = [&](uint16_t* C, int i, int j, ushort4 h) {
     if constexpr (STAGE) {
       *reinterpret_cast<ushort4*>(stage + stage_at(i * 16 + (lane & 15), (j * 16 + 4 * (lane >> 4)) * 2)) = h;
     } else {
-      *reinterpret_cast<ushort4*>(C + (long)(rowb + i * 16) * p.ldc + colb + j * 16) = h;
+      st_out(wt, crs, C, ((long)(rowb + i * 16) * p.ldc + colb + j * 16) * 2, h);
     }
   };
   auto flush = [&](uint16_t* C) {
     if constexpr (STAGE) {  // (one wave's LDS ops complete in order: no barrier needed)
-      uint16_t* Cw = C + (long)(m0 + wr * (WI * 16)) * p.ldc + n0 + wc * (WJ * 16);
+      const long cw = (long)(m0 + wr * (WI * 16)) * p.ldc + n0 + wc * (WJ * 16);
       const int ch = lane & 7;
+      auto rows = [&](auto pol) {
 #pragma unroll
-      for (int k = 0; k < 2 * WI; ++k) {
-        const int row = 8 * k + (lane >> 3);
-        uint4 v = *reinterpret_cast<const uint4*>(stage + row * STAGE_ROW + (((ch ^ (row >> 1)) & 7) << 4));
-        if (row & 1) v = make_uint4(v.z, v.w, v.x, v.y);  // halves stored swapped on odd rows
-        *reinterpret_cast<uint4*>(Cw + (long)row * p.ldc + ch * 8) = v;
-      }
+        for (int k = 0; k < 2 * WI; ++k) {
+          const int row = 8 * k + (lane >> 3);
+          uint4 v = *reinterpret_cast<const uint4*>(stage + row * STAGE_ROW + (((ch ^ (row >> 1)) & 7) << 4));
+          if (row & 1) v = make_uint4(v.z, v.w, v.x, v.y);  // halves stored swapped on odd rows
+          st_pol<decltype(pol)::value>(crs, C, (cw + (long)row * p.ldc + ch * 8) * 2, v);
+        }
+      };
+      if (wt) rows(std::integral_constant<int, ST_SC1>{});
+      else rows(std::integral_constant<int, ST_PLAIN>{});
     }
+  };
+  // this lane's activity word of one 64x64 block (8 bytes) into mask array `mk`
+  auto put_mask = [&](uint64_t* mk, int k, uint64_t word) {
+    uint64_t* mg = mk + mask_word(p, g, 0, 0, 0);  // this model's words
+    const long w = mask_word(p, 0, rowb - (lane & 15) + 64 * k, colb - 4 * (lane >> 4), lane);
+    st_out(wt, store_rsrc(mg), mg, w * 8, word);
   };
 
   constexpr bool CAN_DIE = ENC || EPI == EPI_DC || EPI == EPI_DC_MASK || EPI == EPI_DC_ACT || EPI == EPI_F32;
@@ -203,13 +221,12 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
       for (int i = 0; i < WI; ++i)
 #pragma unroll
         for (int j = 0; j < WJ; ++j)
-          *reinterpret_cast<ushort4*>(C + (long)(rowb + i * 16) * p.ldc + colb + j * 16) = make_ushort4(0, 0, 0, 0);
+          st_out(wt, crs, C, ((long)(rowb + i * 16) * p.ldc + colb + j * 16) * 2, make_ushort4(0, 0, 0, 0));
       if (p.cmask) {
 #pragma unroll
         for (int k = 0; k < WI / 4; ++k) {
-          const long w = mask_word(p, g, rowb - (lane & 15) + 64 * k, colb - 4 * (lane >> 4), lane);
-          p.cmask[w] = 0ull;
-          if (p.cmask2) p.cmask2[w] = 0ull;
+          put_mask(p.cmask, k, 0ull);
+          if (p.cmask2) put_mask(p.cmask2, k, 0ull);
         }
       }
     }
@@ -219,7 +236,7 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
       for (int i = 0; i < WI; ++i)
 #pragma unroll
         for (int j = 0; j < WJ; ++j)
-          *reinterpret_cast<f32x4_t*>(C + (long)(rowb + i * 16) * p.ldc + colb + j * 16) = f32x4_t{0.f, 0.f, 0.f, 0.f};
+          st_out(wt, crs, C, ((long)(rowb + i * 16) * p.ldc + colb + j * 16) * 4, f32x4_t{0.f, 0.f, 0.f, 0.f});
     }
     if constexpr (ENC) {
       for (int idx = tid; idx < (BM / PT) * (BN / PT); idx += NT) {
@@ -251,7 +268,7 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
       // its sub-tile (128-byte rows, the bf16 staging's swizzle) and streams whole 128-byte
       // row segments, 8 rows per dwordx4 store; two passes cover the 64 columns.
       char* st = reinterpret_cast<char*>(red) + wid * (WI * 16 * STAGE_ROW);
-      float* Cw = C + (long)(m0 + wr * (WI * 16)) * p.ldc + n0 + wc * (WJ * 16);
+      const long cw = (long)(m0 + wr * (WI * 16)) * p.ldc + n0 + wc * (WJ * 16);
       const int q = lane >> 4, r16 = lane & 15, ch = lane & 7;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -264,13 +281,17 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
             *reinterpret_cast<float2*>(st + stage_at(row, byte)) = make_float2(v[0], v[1]);
             *reinterpret_cast<float2*>(st + stage_at(row, byte + 8)) = make_float2(v[2], v[3]);
           }
+        auto rows = [&](auto pol) {
 #pragma unroll
-        for (int k = 0; k < WI * 2; ++k) {
-          const int row = 8 * k + (lane >> 3);
-          uint4 u = *reinterpret_cast<const uint4*>(st + row * STAGE_ROW + (((ch ^ (row >> 1)) & 7) << 4));
-          if (row & 1) u = make_uint4(u.z, u.w, u.x, u.y);
-          *reinterpret_cast<uint4*>(Cw + (long)row * p.ldc + h * 32 + ch * 4) = u;
-        }
+          for (int k = 0; k < WI * 2; ++k) {
+            const int row = 8 * k + (lane >> 3);
+            uint4 u = *reinterpret_cast<const uint4*>(st + row * STAGE_ROW + (((ch ^ (row >> 1)) & 7) << 4));
+            if (row & 1) u = make_uint4(u.z, u.w, u.x, u.y);
+            st_pol<decltype(pol)::value>(crs, C, (cw + (long)row * p.ldc + h * 32 + ch * 4) * 4, u);
+          }
+        };
+        if (wt) rows(std::integral_constant<int, ST_SC1>{});
+        else rows(std::integral_constant<int, ST_PLAIN>{});
       }
       return;
     }
@@ -279,7 +300,7 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
 #pragma unroll
       for (int j = 0; j < WJ; ++j) {
         const f32x4_t v = acc[i][j] * alpha;
-        *reinterpret_cast<f32x4_t*>(C + (long)(rowb + i * 16) * p.ldc + colb + j * 16) = v;
+        st_out(wt, crs, C, ((long)(rowb + i * 16) * p.ldc + colb + j * 16) * 4, v);
       }
     return;
   }
@@ -430,9 +451,8 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
     if (p.cmask) {
 #pragma unroll
       for (int k = 0; k < WI / 4; ++k) {
-        const long w = mask_word(p, g, rowb - (lane & 15) + 64 * k, colb - 4 * (lane >> 4), lane);
-        p.cmask[w] = ((uint64_t)mw[k][1] << 32) | mw[k][0];
-        if (ACTV && act == 2 && p.cmask2) p.cmask2[w] = ((uint64_t)qw[k][1] << 32) | qw[k][0];
+        put_mask(p.cmask, k, ((uint64_t)mw[k][1] << 32) | mw[k][0]);
+        if (ACTV && act == 2 && p.cmask2) put_mask(p.cmask2, k, ((uint64_t)qw[k][1] << 32) | qw[k][0]);
         if (l0_from_mask) l0 += (float)(__popc(mw[k][0]) + __popc(mw[k][1]));
       }
     }
@@ -997,7 +1017,11 @@ __device__ __forceinline__ void gemm_block(const GemmParams& p, const int bid, c
   SC_SUB(6);
   constexpr bool STAGE = (S::WI == 4 || S::WI == 8) && S::WJ == 4 && NST * STG >= stage_bytes<S>();
   constexpr bool FSTAGE = EPI == EPI_F32 && S::WJ == 4 && NST * STG >= S::NW * S::WI * 16 * STAGE_ROW;
-  sae_epilogue<S, EPI, AUX_EARLY, STAGE, FSTAGE>(p, acc, auxv, biasv, mkv, reinterpret_cast<float*>(smem), pi, g, m0, n0, tn,
+  // Two instantiations that already spill keep plain stores at compile time (the second store form
+  // grew their scratch: 72 -> 200 and 300 -> 344 bytes per lane): the fp32 epilogue on the pipelined
+  // 128x128 BK32 x 3 ring and the counting encoder on the eight-wave 256x128 block.  Neither is a default.
+  constexpr bool WTC = !(P32 && NST == 3 && EPI == EPI_F32) && !(NW == 8 && BN == 128 && NST == 3 && EPI == EPI_ENC_CNT);
+  sae_epilogue<S, EPI, AUX_EARLY, STAGE, FSTAGE, WTC>(p, acc, auxv, biasv, mkv, reinterpret_cast<float*>(smem), pi, g, m0, n0, tn,
                                                  tiles_n, cptr, alpha, dead);
   SC_STAMP(3);
 }

@@ -14,7 +14,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, store_policy
 
 EPI_ENC, EPI_DEC, EPI_DC, EPI_F32, EPI_BF16, EPI_ENC_CNT, EPI_DC_MASK = 0, 1, 2, 3, 4, 6, 7
 EPI_ENC_ACT, EPI_DC_ACT, EPI_ROWMAX = 8, 9, 10
@@ -176,6 +176,9 @@ def _launch(epi, layout, M, N, K1, K2, G, a_ops, b_ops, outs, alphas, ldc, sc, *
     al = (C.c_float * nprob)(*alphas)
     # host copy of a masked ensemble's live sizes: the launcher then launches only live tiles
     nh = (C.c_int * len(nact_host))(*[int(v) for v in nact_host]) if nact_host is not None else None
+    # output tiles written through the L2 (ops/store_policy.py), while one model's output is addressable
+    esize = 4 if epi in (EPI_F32, EPI_ROWMAX) else 2
+    store_wt = store_policy.gemm_write_through(epi, store_policy.output_span_bytes(M, N, ldc, esize))
     rc = _lib.lib().sc_gemm(
         epi, layout, nprob, M, N, K1, K2, G, A, Bo, Cp, al, ldc, sc,
         _lib.ptr(bias), sbias, _lib.ptr(nactive), _lib.ptr(aux), ldaux, saux,
@@ -183,7 +186,7 @@ def _launch(epi, layout, M, N, K1, K2, G, a_ops, b_ops, outs, alphas, ldc, sc, *
         _lib.ptr(dotpart), int(bool(dc_tied)),
         cfg, int(ksplit), int(split_stride), _lib.ptr(cmask), int(act), _lib.ptr(ascale),
         _lib.ptr(cmask2), _lib.ptr(rcol), _lib.ptr(nact_m), _lib.ptr(nact_k),
-        C.cast(nh, C.c_void_p) if nh is not None else None, _lib.stream_handle(),
+        C.cast(nh, C.c_void_p) if nh is not None else None, _lib.stream_handle(), int(store_wt),
     )
     _lib.check(rc, f"sc_gemm(epi={epi})")
 
