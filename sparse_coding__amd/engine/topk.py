@@ -26,6 +26,10 @@ k differs, ``autoencoders/ensemble.py:100-116``; math of ``autoencoders/topk_enc
 
 ``enable_graph()`` captures the whole step as one HIP graph (two, alternating the pick buffers:
 step t clears step t-1's picks).
+
+Per-feature quantities come from the picks, never from a dense [G, B, n] code matrix
+(``ops/topk_stats.py``): window fire counts inside the step (``count_every``), ``evaluate``,
+``resample_dead`` and ``feature_stats`` on a forward-only pass with pick buffers of its own.
 """
 
 from __future__ import annotations
@@ -38,6 +42,7 @@ import torch
 from ..ops import adam as adam_ops
 from ..ops import gemm as gemm_ops
 from ..ops import topk as topk_ops
+from ..ops import topk_stats as tstats_ops
 
 # Cost model of the weight gradient per model (MI355X, measured on config 4): the slot-list
 # kernel moves ~4 d bytes per pick at ~5 TB/s from L2 / MALL; the dense two-segment GEMM does
@@ -56,7 +61,7 @@ def auto_sparse_k(B: int, n: int, d: int, margin: float = 1.3) -> int:
 class FusedTopKEnsemble:
     def __init__(self, models, sig=None, lr=1e-3, batch_size=256, device="cuda", betas=(0.9, 0.999), eps=1e-8,
                  grad_dtype: str = "bf16", sparse_k: Union[int, str] = "auto", scores_dtype: Optional[str] = None,
-                 fused_tail: bool = True):
+                 fused_tail: bool = True, count_every: int = 0):
         from ..models.topk import TopKEncoder
 
         self.sig = sig or TopKEncoder
@@ -128,6 +133,16 @@ class FusedTopKEnsemble:
         self.use_graph = False
         self._graphs = None
         self._src_graphs = None
+        # window fire counts: every `count_every`-th step histograms its picks (0: off -- nothing is
+        # allocated and the step launches what it always did); `rows_seen` counts those steps' rows
+        self.count_every = int(count_every)
+        if self.count_every < 0:
+            raise ValueError(f"count_every must be >= 0, got {count_every}")
+        self.feature_counts = torch.zeros(G, n, device=dev, dtype=torch.int64) if self.count_every else None
+        self.rows_seen = 0
+        self._ks = ks
+        self._fwd = None    # (idx, val) of the forward-only pass
+        self._stat_lists = None
 
     # ------------------------------------------------------------------ the step
     def _step_kernels(self, x, cur: int, gather=None):
@@ -135,6 +150,9 @@ class FusedTopKEnsemble:
         idx, prev = self.idx_buf[cur], self.idx_buf[1 - cur]
         gemm_ops.matmul_nt(x, self.shadow, self.scores)
         topk_ops.topk_select(self.scores, self.k, self.kmax, out=(idx, self.val), x=x, D=self.shadow)
+        if self.count_every:
+            # the device decides (step_dev % count_every == 0): one captured graph serves every step
+            tstats_ops.pick_counts(idx, self.val, self.k, self.feature_counts, self.step_dev, self.count_every)
         topk_ops.decode_grad(idx, self.val, self.k, self.shadow, x, self.r, self.row_se, self.codebuf,
                              self.dscbuf, dscv=self.dscv, prev_idx=prev, dense_from=self._dense_from)
         alpha = 2.0 / (B * d)
@@ -186,8 +204,16 @@ class FusedTopKEnsemble:
             self._step_kernels(x, self._cur)
         self.idx = self.idx_buf[self._cur]
         self._cur ^= 1
+        self.rows_seen += self.batch_size * self._counting_steps(self.step_count, 1)
         self.step_count += 1
         return self.mse
+
+    def _counting_steps(self, t0: int, steps: int) -> int:
+        """How many of the steps t0 .. t0 + steps - 1 count their picks (t % count_every == 0)."""
+        c = self.count_every
+        if not c:
+            return 0
+        return (t0 + steps + c - 1) // c - (t0 + c - 1) // c
 
     def _capture_source(self, source, steps: int, cur0: int):
         torch.cuda.synchronize(self.device)
@@ -223,8 +249,186 @@ class FusedTopKEnsemble:
         last = self._cur ^ ((steps - 1) & 1)
         self.idx = self.idx_buf[last]
         self._cur = last ^ 1
+        self.rows_seen += self.batch_size * self._counting_steps(self.step_count, steps)
         self.step_count += steps
         return self.mse
+
+    # ------------------------------------------------------------------ fire counts, evaluation, resampling, statistics
+    def feature_frequency(self) -> torch.Tensor:
+        """Per-feature firing frequency [G, n] = feature_counts / rows_seen over the steps that counted
+        (every ``count_every``-th; exact for ``count_every=1``) since the last reset.  A firing is a pick
+        with a positive code: a pick whose score the ReLU clamped to 0 does not count."""
+        if self.feature_counts is None:
+            raise RuntimeError("feature counting is off (count_every=0)")
+        return self.feature_counts / max(1, self.rows_seen)
+
+    def _x_bf16(self, rows):
+        return rows.to(self.device, torch.bfloat16).contiguous()
+
+    def _forward_only(self, x, decode: bool = True):
+        """Scores, select and (``decode``) residual of one bf16 batch ``x`` [B, d] without gradients, as
+        the training step computes them (the scores GEMM into ``scores``, the select with the exact tie
+        resolve) but with pick buffers of its own: ``idx_buf``, the parity, the dense code / code-gradient
+        buffers, ``dscv``, ``mse``, the step counter, the parameters and captured graphs are untouched
+        (the dense buffers must keep holding exactly the previous parity's picks).  Overwrites the
+        scratch ``scores`` / ``r`` / ``row_se``, which every training step rewrites before reading.
+        Returns the picks (idx, val)."""
+        if self._fwd is None:
+            G, B, kmax = self.n_models, self.batch_size, self.kmax
+            self._fwd = (torch.zeros(G, B, kmax, device=self.device, dtype=torch.int32),
+                         torch.zeros(G, B, kmax, device=self.device))
+        idx, val = self._fwd
+        gemm_ops.matmul_nt(x, self.shadow, self.scores)
+        topk_ops.topk_select(self.scores, self.k, self.kmax, out=(idx, val), x=x, D=self.shadow)
+        if decode:  # (no dense buffers: the kernel returns after row_se, nothing is scattered or cleared)
+            topk_ops.decode_grad(idx, val, self.k, self.shadow, x, self.r, self.row_se, None, None)
+        return idx, val
+
+    def _check_rows(self, rows, what: str):
+        if rows.dim() != 2 or rows.shape[1] != self.d:
+            raise ValueError(f"rows must be [N, {self.d}], got {tuple(rows.shape)}")
+        N = rows.shape[0]
+        if N <= 0 or N % self.batch_size:
+            raise ValueError(f"{what} needs a positive multiple of the batch size ({self.batch_size}) rows, got {N}")
+        return N
+
+    @torch.no_grad()
+    def evaluate(self, rows: torch.Tensor):
+        """FVU and mean L0 of every model on ``rows`` [N, d] (trimmed to a multiple of the batch size):
+        the squared error from the decode's per-row sums, the variance bookkeeping in fp64, L0 the mean
+        number of positive codes per row.  Returns (fvu [G], l0 [G]) on the device; never synchronises."""
+        B, G = self.batch_size, self.n_models
+        if rows.dim() != 2 or rows.shape[1] != self.d:
+            raise ValueError(f"rows must be [N, {self.d}], got {tuple(rows.shape)}")
+        N = rows.shape[0] - rows.shape[0] % B
+        if N == 0:
+            raise ValueError(f"need at least {B} rows")
+        f64 = torch.float64
+        se = torch.zeros(G, device=self.device, dtype=f64)
+        l0 = torch.zeros(G, device=self.device, dtype=f64)
+        s1 = torch.zeros(self.d, device=self.device, dtype=f64)
+        s2 = torch.zeros((), device=self.device, dtype=f64)
+        for i in range(0, N, B):
+            x = self._x_bf16(rows[i:i + B])
+            _, val = self._forward_only(x)
+            se += self.row_se.sum(1, dtype=f64)
+            l0 += (val > 0).sum((1, 2)).double()  # (the padded slots hold 0.0)
+            xf = x.double()
+            s1 += xf.sum(0)
+            s2 += xf.pow(2).sum()
+        var = s2 - s1.pow(2).sum() / N  # total sum of squares about the mean
+        return (se / var).float(), (l0 / N).float()
+
+    @torch.no_grad()
+    def resample_dead(self, rows: torch.Tensor, *, pick: str = "worst", ratio: float = 1.0,
+                      use_window_counts: bool = True, generator: Optional[torch.Generator] = None,
+                      rule: Optional[str] = None) -> torch.Tensor:
+        """Re-seed dead atoms from badly reconstructed rows of the candidate pool ``rows`` [N, d] (N a
+        positive multiple of the batch size); returns the per-model number of resampled atoms as a
+        device tensor [G].  Never synchronises; captured step graphs stay valid.
+
+        The pool is scored forward-only, batch by batch: the decode's per-row squared errors and the
+        fire counts of the picks (a pick with code 0 is not a firing).  Atom (g, f) is dead when it never
+        fires on the pool and -- ``use_window_counts``, if the engine counts (``count_every > 0``) and has
+        counted rows since the last reset -- has ``feature_counts[g, f] == 0`` too.
+        ``engine.resample.plan_resample`` pairs the dead atoms (ascending) with pool rows (``pick``), and
+        one ``sc_resample_dict_rows`` launch writes master row <- unit pool row x scale[g], zeroes its
+        Adam moments and rewrites its bf16 shadow row and row norm.  scale[g] = ``ratio`` x the mean
+        master-row norm of the alive atoms (of all atoms if none is alive): the dictionary is used
+        normalised, so the master norm does not change the forward pass -- it only sets Adam's RELATIVE
+        step on the row, and ``ratio = 1.0`` keeps that the same as for the row's neighbours.  There is
+        one rewrite rule here: ``rule`` (the SAE engines' keyword, which the sweep driver passes) is
+        accepted and ignored.  Afterwards ``feature_counts`` and ``rows_seen`` are reset."""
+        from ..ops import resample as rs_ops
+        from . import resample as rs
+        from . import topk_stats as ts
+
+        if pick not in rs.PICKS:
+            raise ValueError(f"pick must be one of {rs.PICKS}, got {pick!r}")
+        N = self._check_rows(rows, "the pool")
+        B, G, n, dev = self.batch_size, self.n_models, self.n, self.device
+        pool = self._x_bf16(rows)
+        err = torch.empty(G, N, device=dev)
+        fired = torch.zeros(G, n, device=dev, dtype=torch.int64)
+        for i in range(0, N, B):
+            idx, val = self._forward_only(pool[i:i + B])
+            err[:, i:i + B].copy_(self.row_se)
+            tstats_ops.pick_counts(idx, val, self.k, fired)
+        dead = fired == 0
+        if use_window_counts and self.feature_counts is not None and self.rows_seen > 0:
+            dead &= self.feature_counts == 0
+        dead_idx, src_idx, cnt = rs.plan_resample(dead, err, pick=pick, generator=generator)
+        scale = ts.resample_dict_scales(self.params["dict"], dead, ratio)
+        rs_ops.resample_dict_rows(dead_idx, src_idx, cnt, pool, scale, self.params["dict"], self.m["dict"],
+                                  self.v["dict"], self.shadow, self.norms, normalize_src=True)
+        if self.feature_counts is not None:
+            self.feature_counts.zero_()
+        self.rows_seen = 0
+        return cnt
+
+    @torch.no_grad()
+    def feature_stats(self, rows: torch.Tensor, *, topk: int = 0, row_offset: int = 0, state=None):
+        """Per-feature activation statistics of every model on ``rows`` [N, d] (N a positive multiple of
+        the batch size): an ``engine.feature_stats.FeatureStats`` with the SAE engine's argument contract
+        (``topk`` in 0..32, ``row_offset``, continuation through ``state``).  Never synchronises.
+
+        Per batch: the forward-only select (no decode), the feature-major slot lists of ALL models
+        (``sc_topk_slot_lists`` into buffers of this method's own, not the training step's) and one
+        ``pick_stats`` launch that walks every feature's list in row order -- no dense code matrix.  Only
+        positive codes take part; a feature nobody picks reads count 0, max 0.0 and rows of -1, as
+        the dense reduction would.  Bit-reproducible, and chunk by chunk through ``state`` gives the
+        bits of one call on the whole pool.  Parameters, moments, shadows, window counts, the step
+        counter and captured graphs are left as they are."""
+        from . import feature_stats as fs
+
+        N = self._check_rows(rows, "feature_stats")
+        B, G, n, dev = self.batch_size, self.n_models, self.n, self.device
+        topk, row_offset = fs.check_request(topk, row_offset, state, G, n)
+        if self._stat_lists is None:
+            self._stat_lists = topk_ops.SlotLists(G, B, n, self._ks, self.kmax, dev)
+        tv = tr = None
+        if state is None:
+            acc = torch.zeros(G, 5, n, device=dev, dtype=torch.float64)  # count, sum c .. sum c^4
+            mx = torch.zeros(G, n, device=dev)
+            if topk:
+                tv, tr = fs.empty_topk(G, n, topk, dev)
+            seen = 0
+        else:
+            acc = torch.cat([state.count.to(dev, torch.float64).unsqueeze(1), state.sums.to(dev)], dim=1).contiguous()
+            mx = state.max.to(dev, copy=True).contiguous()
+            if topk:
+                tv = state.top_vals.to(dev, copy=True).contiguous()
+                tr = state.top_rows.to(dev, copy=True).contiguous()
+            seen = int(state.n_rows)
+        pool = self._x_bf16(rows)
+        for i in range(0, N, B):
+            idx, val = self._forward_only(pool[i:i + B], decode=False)
+            topk_ops.slot_lists(idx, self.k, self._stat_lists)  # (leaves its counters zero for the next batch)
+            tstats_ops.pick_stats(self._stat_lists, val, acc, mx, tv, tr, row_offset + i)
+        return fs.FeatureStats(seen + N, acc[:, 0].round().to(torch.int64), acc[:, 1:].contiguous(), mx, tv, tr)
+
+    def state_dict(self):
+        """Masters, moments and the step; with ``count_every > 0`` also the window counts."""
+        sd = {"params": self.params, "m": self.m, "v": self.v, "step": self.step_count}
+        if self.feature_counts is not None:
+            sd["feature_counts"], sd["rows_seen"] = self.feature_counts, self.rows_seen
+        return sd
+
+    def load_state_dict(self, sd):
+        """Counts and ``rows_seen`` are optional (checkpoints from before the engine counted)."""
+        for d_ in ("params", "m", "v"):
+            for k, t in sd[d_].items():
+                getattr(self, d_)[k].copy_(t)
+        self.step_count = int(sd["step"])
+        self.step_dev.fill_(self.step_count)
+        adam_ops.shadow_rows(self.params["dict"], self.shadow, self.norms, normalize=True)
+        if self.feature_counts is not None:
+            if sd.get("feature_counts") is not None:
+                self.feature_counts.copy_(sd["feature_counts"])
+                self.rows_seen = int(sd.get("rows_seen", 0))
+            else:
+                self.feature_counts.zero_()
+                self.rows_seen = 0
 
     # ------------------------------------------------------------------ inference / export
     def encode(self, x):

@@ -284,15 +284,17 @@ class EnsembleTrainer:
 
         The fused SAE engine runs ``FusedSAEEnsemble.resample_dead`` (N a multiple of its batch size;
         under ensemble sharding each rank resamples its own models from the rows it is given, N a
-        multiple of the engine's global batch).  The analytic and eager engines with an untied / tied
-        SAE signature run the same rules in fp32 torch: dead means "never fires on ``rows``".  Data
-        parallel trainers and every other kind raise ``NotImplementedError``."""
+        multiple of the engine's global batch).  The fused top-k engine runs
+        ``FusedTopKEnsemble.resample_dead`` (one rule: ``rule`` is accepted and ignored).  The analytic
+        and eager engines with an untied / tied SAE signature run the same rules in fp32 torch: dead
+        means "never fires on ``rows``".  Data parallel trainers and every other kind (top-k under the
+        eager engine included) raise ``NotImplementedError``."""
         from . import resample as rs
 
         if self.dp is not None:
             raise NotImplementedError("resample_dead: data-parallel replicas (parallel='dp'/'zero1') would need "
                                       "a common candidate pool on every rank")
-        if self.kind == "fused-sae":
+        if self.kind in ("fused-sae", "fused-topk"):
             cnt = self.impl.resample_dead(rows.to(self.device), **kw)
             return [int(c) for c in cnt.cpu()]
         kind = analytic._KINDS.get(self.sig)
@@ -324,15 +326,17 @@ class EnsembleTrainer:
 
         The fused SAE engine runs ``FusedSAEEnsemble.feature_stats`` (N a multiple of its batch size;
         under ensemble sharding each rank gets the statistics of its own models on the rows it is given,
-        N a multiple of the engine's global batch).  The analytic and eager engines with an untied / tied
-        SAE signature run the fp64 oracle on their fp32 torch codes, ``batch_size`` rows at a time.
-        Data-parallel trainers and every other kind raise ``NotImplementedError``."""
+        N a multiple of the engine's global batch).  The fused top-k engine runs
+        ``FusedTopKEnsemble.feature_stats`` (from the picks, no dense codes).  The analytic and eager
+        engines with an untied / tied SAE signature run the fp64 oracle on their fp32 torch codes,
+        ``batch_size`` rows at a time.  Data-parallel trainers and every other kind (top-k under the
+        eager engine included) raise ``NotImplementedError``."""
         from . import feature_stats as fs
 
         if self.dp is not None:
             raise NotImplementedError("feature_stats: data-parallel replicas (parallel='dp'/'zero1') hold the same "
                                       "models on different rows; collect the statistics on one rank's engine")
-        if self.kind == "fused-sae":
+        if self.kind in ("fused-sae", "fused-topk"):
             return self.impl.feature_stats(rows.to(self.device), **kw)
         kind = analytic._KINDS.get(self.sig)
         if self.kind not in ("analytic", "eager") or kind is None:
@@ -412,8 +416,7 @@ class EnsembleTrainer:
         elif self.kind == "fused-sae":
             st["impl"] = self.impl.state_dict()
         elif self.kind == "fused-topk":
-            st["impl"] = {"params": self.impl.params, "m": self.impl.m, "v": self.impl.v,
-                          "step": self.impl.step_count}
+            st["impl"] = self.impl.state_dict()
         elif self.kind in ("analytic", "fista-loss", "fista-loss-fused", "unrolled"):
             st["impl"] = self.impl.state_dict()
         else:
@@ -438,14 +441,7 @@ class EnsembleTrainer:
             for c, zst in zip(self.dp.chunks, imp["zero"]):
                 c.load_state_dict(zst)
         elif self.kind == "fused-topk":
-            for d_ in ("params", "m", "v"):
-                for k, t in imp[d_].items():
-                    getattr(self.impl, d_)[k].copy_(t)
-            self.impl.step_count = int(imp["step"])
-            self.impl.step_dev.fill_(self.impl.step_count)
-            from ..ops import adam as adam_ops
-
-            adam_ops.shadow_rows(self.impl.params["dict"], self.impl.shadow, self.impl.norms, normalize=True)
+            self.impl.load_state_dict(imp)
         else:
             from torch.utils import _pytree as pytree
 

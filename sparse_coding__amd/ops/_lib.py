@@ -69,6 +69,12 @@ def signatures():
                                  c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
         "sc_topk_slot_lists": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                c_int, c_int, c_void_p],
+        "sc_topk_pick_counts": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                c_void_p],
+        "sc_topk_pick_stats": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                               c_int, c_int, c_int, c_long, c_long, c_void_p],
+        "sc_resample_dict_rows": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
         "sc_topk_clear": [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p],
         "sc_topk_scatter": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p],
         "sc_fista": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

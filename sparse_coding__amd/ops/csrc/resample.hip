@@ -11,6 +11,8 @@
 //     bias[g, f]         <- 0 if zero_bias;                                              m, v <- 0
 //   and the bf16 shadows / row norms of the rewritten rows through shadow_row (row_adam.h), the body
 //   of sc_shadow_rows: the same reduction order, the same bits.
+//   The three bias pointers may be null (sc_resample_dict_rows: a normalised dictionary with no bias,
+//   the top-k ensembles): the dictionary goes in the enc* slots with norms given, decoder null.
 //   (Anthropic's "Towards Monosemanticity" resampling; reference experiments/huge_batch_size.py:
 //   224-250 is the un-normalised, encoder-only case.)
 #include "common.h"
@@ -50,7 +52,7 @@ struct ResampleArgs {
   uint16_t* enc_shadow;
   float *dec, *dec_m, *dec_v;  // null: tied dictionary
   uint16_t* dec_shadow;
-  float *bias, *bias_m, *bias_v;  // [G][n]
+  float *bias, *bias_m, *bias_v;  // [G][n]; all null: no bias
   float* norms;                   // [G][n] row norms of the normalised dictionary
   int G, n, d;
 };
@@ -97,9 +99,9 @@ __global__ __launch_bounds__(256) void resample_rows_kernel(ResampleArgs a) {
     }
   }
   if (lane == 0) {
-    if (a.zero_bias) a.bias[row] = 0.f;
-    a.bias_m[row] = 0.f;
-    a.bias_v[row] = 0.f;
+    if (a.zero_bias && a.bias) a.bias[row] = 0.f;
+    if (a.bias_m) a.bias_m[row] = 0.f;
+    if (a.bias_v) a.bias_v[row] = 0.f;
   }
   // shadows and norms of the rows that changed, from the masters just written (each lane reads back
   // exactly the elements it stored)
@@ -125,6 +127,20 @@ int sc_row_sqerr(const void* r, float* err, int G, int B, int d, long N, long of
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
+static int launch_resample(const ResampleArgs& a, int P, hipStream_t stream) {
+  const long blocks = ((long)a.G * P + 3) / 4;
+#define SC_RESAMPLE(NVV)                                                                        \
+  case NVV:                                                                                     \
+    hipLaunchKernelGGL((resample_rows_kernel<NVV>), dim3(blocks), dim3(256), 0, stream, a);     \
+    break;
+  switch (a.d / 256) {
+    SC_RESAMPLE(1) SC_RESAMPLE(2) SC_RESAMPLE(3) SC_RESAMPLE(4) SC_RESAMPLE(6) SC_RESAMPLE(8) SC_RESAMPLE(16)
+    default: return 1;
+  }
+#undef SC_RESAMPLE
+  return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
 int sc_resample_rows(const int* dead_idx, const long* src_idx, const int* cnt, int P, const void* rows, long N,
                      const float* enc_scale, int normalize_src, int set_decoder, int zero_bias, float* enc,
                      float* enc_m, float* enc_v, void* enc_shadow, float* dec, float* dec_m, float* dec_v,
@@ -143,17 +159,26 @@ int sc_resample_rows(const int* dead_idx, const long* src_idx, const int* cnt, i
   a.dec = dec; a.dec_m = dec_m; a.dec_v = dec_v; a.dec_shadow = reinterpret_cast<uint16_t*>(dec_shadow);
   a.bias = bias; a.bias_m = bias_m; a.bias_v = bias_v; a.norms = norms;
   a.G = G; a.n = rows_per_model; a.d = d;
-  const long blocks = ((long)G * P + 3) / 4;
-#define SC_RESAMPLE(NVV)                                                                        \
-  case NVV:                                                                                     \
-    hipLaunchKernelGGL((resample_rows_kernel<NVV>), dim3(blocks), dim3(256), 0, stream, a);     \
-    break;
-  switch (d / 256) {
-    SC_RESAMPLE(1) SC_RESAMPLE(2) SC_RESAMPLE(3) SC_RESAMPLE(4) SC_RESAMPLE(6) SC_RESAMPLE(8) SC_RESAMPLE(16)
-    default: return 1;
-  }
-#undef SC_RESAMPLE
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return launch_resample(a, P, stream);
+}
+
+// A normalised dictionary with no bias and no separate decoder (the top-k ensembles): row dead_idx[g, j]
+// of `dict` <- u scale[g] (u the unit pool row if normalize_src, else the raw row), m, v <- 0, and the
+// normalised bf16 shadow / row norm of the row through shadow_row.
+int sc_resample_dict_rows(const int* dead_idx, const long* src_idx, const int* cnt, int P, const void* rows, long N,
+                          const float* scale, int normalize_src, float* dict, float* dict_m, float* dict_v,
+                          void* shadow, float* norms, int G, int rows_per_model, int d, hipStream_t stream) {
+  if (d % 256 || d > 4096 || G < 1 || P < 1 || N < 1 || rows_per_model < 1) return 1;
+  if (!dead_idx || !src_idx || !cnt || !rows || !scale || !dict || !dict_m || !dict_v || !shadow || !norms) return 1;
+  ResampleArgs a;
+  a.dead_idx = dead_idx; a.src_idx = src_idx; a.cnt = cnt; a.P = P;
+  a.rows = reinterpret_cast<const uint16_t*>(rows); a.N = N; a.enc_scale = scale;
+  a.normalize_src = normalize_src; a.set_decoder = 0; a.zero_bias = 0;
+  a.enc = dict; a.enc_m = dict_m; a.enc_v = dict_v; a.enc_shadow = reinterpret_cast<uint16_t*>(shadow);
+  a.dec = a.dec_m = a.dec_v = nullptr; a.dec_shadow = nullptr;
+  a.bias = a.bias_m = a.bias_v = nullptr; a.norms = norms;
+  a.G = G; a.n = rows_per_model; a.d = d;
+  return launch_resample(a, P, stream);
 }
 
 }  // extern "C"

@@ -76,3 +76,43 @@ def resample_rows(dead_idx, src_idx, cnt, rows, enc_scale, enc, enc_m, enc_v, en
         _lib.ptr(enc_v), _lib.ptr(enc_shadow), _lib.ptr(dec), _lib.ptr(dec_m), _lib.ptr(dec_v), _lib.ptr(dec_shadow),
         _lib.ptr(bias), _lib.ptr(bias_m), _lib.ptr(bias_v), _lib.ptr(norms), G, n, d, _lib.stream_handle())
     _lib.check(rc, "sc_resample_rows")
+
+
+def resample_dict_rows(dead_idx, src_idx, cnt, rows, scale, dict_, dict_m, dict_v, shadow, norms, *,
+                       normalize_src: bool = True):
+    """``resample_rows`` for a normalised dictionary with no bias and no separate decoder (the top-k
+    ensembles): row ``dead_idx[g, j]`` (j < ``cnt[g]``, read on the device) of ``dict_`` fp32 [G, n, d] <-
+    u scale[g] with u = x / max(|x|, 1e-8) of the pool row x = ``rows[src_idx[g, j]]`` (``normalize_src``;
+    else x itself), its moments <- 0, and its normalised bf16 ``shadow`` row and ``norms`` entry rewritten
+    with the bits of an ``adam.shadow_rows(normalize=True)`` pass.  Nothing here synchronises; the
+    launch is graph-capturable."""
+    if dict_.dim() != 3:
+        raise ValueError("dict_ must be [G, n, d]")
+    G, n, d = dict_.shape
+    dev = dict_.device
+    if d % 256 or d > 4096:
+        raise ValueError(f"resample_dict_rows needs d % 256 == 0, d <= 4096 (got {d})")
+
+    def need(t, name, dtype, shape):
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be contiguous {dtype} {tuple(shape)} on {dev}")
+
+    if dead_idx.dim() != 2 or dead_idx.shape[0] != G or dead_idx.shape[1] < 1:
+        raise ValueError("dead_idx must be int32 [G, P] with P >= 1")
+    P = dead_idx.shape[1]
+    need(dead_idx, "dead_idx", torch.int32, (G, P))
+    need(src_idx, "src_idx", torch.int64, (G, P))
+    need(cnt, "cnt", torch.int32, (G,))
+    need(scale, "scale", torch.float32, (G,))
+    if rows.dim() != 2 or rows.shape[0] < 1:
+        raise ValueError("rows must be bf16 [N, d] with N >= 1")
+    need(rows, "rows", torch.bfloat16, (rows.shape[0], d))
+    for name, t in (("dict_", dict_), ("dict_m", dict_m), ("dict_v", dict_v)):
+        need(t, name, torch.float32, (G, n, d))
+    need(shadow, "shadow", torch.bfloat16, (G, n, d))
+    need(norms, "norms", torch.float32, (G, n))
+    rc = _lib.lib().sc_resample_dict_rows(
+        _lib.ptr(dead_idx), _lib.ptr(src_idx), _lib.ptr(cnt), P, _lib.ptr(rows), rows.shape[0], _lib.ptr(scale),
+        int(bool(normalize_src)), _lib.ptr(dict_), _lib.ptr(dict_m), _lib.ptr(dict_v), _lib.ptr(shadow),
+        _lib.ptr(norms), G, n, d, _lib.stream_handle())
+    _lib.check(rc, "sc_resample_dict_rows")
