@@ -44,7 +44,7 @@ __global__ __launch_bounds__(TK_NT, 4) void topk_select_kernel(const float* __re
   __shared__ int sel[2];  // selected digit, keys strictly above it
   const long row = blockIdx.x;
   const int g = row / B;
-  const int k = min(kv[g], n);
+  const int k = min(min(kv[g], n), kmax);  // the output rows are kmax wide
   const float* S = scores + row * n;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint32_t key[PER];
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void topk_wave_kernel(const float* __restrict_
   const long row = (long)blockIdx.x * 4 + w;
   if (row >= rows) return;          // per-wave work only: no block barrier below
   const int g = (int)(row / B);
-  const int k = min(kv[g], n);
+  const int k = min(min(kv[g], n), kmax);  // the output rows are kmax wide
   const float* S = reinterpret_cast<const float*>(__builtin_assume_aligned(scores + row * n, 16));
   int* I = idx + row * kmax;
   float* V = val + row * kmax;
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void topk_block_kernel(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const long row = blockIdx.x;
   const int g = (int)(row / B);
-  const int k = min(kv[g], n);
+  const int k = min(min(kv[g], n), kmax);  // the output rows are kmax wide
   const float* S = reinterpret_cast<const float*>(__builtin_assume_aligned(scores + row * n, 16));
   int* I = idx + row * kmax;
   float* V = val + row * kmax;
@@ -617,7 +617,9 @@ __global__ __launch_bounds__(256) void topk_block_kernel(const float* __restrict
 // and keeps the largest, ties to the lower column.  Kept values are the bf16 scores (after ReLU): the
 // precision the codes are stored in downstream.  Same bracket as topk_block_kernel (16-bit bisections);
 // more than BR_CAP keys at the bracket (heavy ties, e.g. an all-zero row) fall back to a full
-// bisection with ties taken in column order.
+// bisection with ties taken in column order.  Ties that are not ranked exactly (no operands, or more
+// than TIE_CAP of them) are taken in column order on the bracket path too: its candidates are in
+// thread-major order, which is column order only for n <= 2048, so that branch takes them chunk by chunk.
 __device__ __forceinline__ uint32_t order16(uint32_t h) {
   return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);  // larger bf16 -> larger key
 }
@@ -727,6 +729,54 @@ __device__ __forceinline__ bool bracket_select16(const uint32_t (&key)[PL], int 
         tkeep[lane] = rank < need ? 1 : 0;
       }
     }
+    if (PL > 8 && !exact && nt > need) {
+      // more ties than slots and no exact ranking: take the `need` lowest columns.  The candidates
+      // are in thread-major order (thread, chunk, j), which is column order only within one chunk
+      // of 2048 columns (so PL = 8 needs none of this).  Count the ties of every chunk, find the
+      // chunk `cstar` that holds the need-th lowest tied column, and take the ties of the chunks
+      // before it and the first `rem` of its own.  A rare path: rolled loops over the candidates in
+      // LDS, apart from the loop below, which keeps its instruction stream.
+      int cc[PL / 8];
+#pragma unroll
+      for (int i = 0; i < PL / 8; ++i) cc[i] = 0;
+#pragma unroll 1
+      for (int p = lane; p < total; p += 64) {
+        const int ch = ckey[p] == t ? ccol[p] >> 11 : -1;
+#pragma unroll
+        for (int i = 0; i < PL / 8; ++i) cc[i] += ch == i ? 1 : 0;
+      }
+      int cstar = PL / 8, rem = need;
+#pragma unroll
+      for (int i = 0; i < PL / 8; ++i) {
+        const int c = wave_total(cc[i]);
+        if (cstar == PL / 8) {
+          if (rem <= c) cstar = i;
+          else rem -= c;
+        }
+      }
+      int base = 0, seen = 0;
+#pragma unroll 1
+      for (int p0 = 0; p0 < total; p0 += 64) {
+        const int p = p0 + lane;  // < BR_CAP
+        const bool in = p < total;
+        const uint32_t kk = in ? ckey[p] : 0u;
+        const int col = in ? ccol[p] : 0;
+        const int ch = col >> 11;
+        const bool eq = in && kk == t;
+        const uint64_t ms = __ballot(eq && ch == cstar);
+        const bool take = kk > t || (eq && (ch < cstar || (ch == cstar && seen + lanes_below(ms) < rem)));
+        const uint64_t mt = __ballot(take);
+        if (take) {
+          const int pos = base + lanes_below(mt);
+          const float sv = bf2f(S[col]);
+          I[pos] = col;
+          V[pos] = relu ? fmaxf(sv, 0.f) : sv;
+        }
+        base += __popcll(mt);
+        seen += __popcll(ms);
+      }
+      return true;
+    }
     int base = 0, ties = 0;
 #pragma unroll
     for (int q = 0; q < BR_CAP / 64; ++q) {
@@ -770,7 +820,7 @@ __global__ __launch_bounds__(256) void topk_bf16_kernel(const uint16_t* __restri
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b = (int)(blockIdx.x % B), g = (int)(blockIdx.x / B);
   const long row = (long)g * B + b;  // scores row [G][B][n]; idx / val are [G][B][kmax]
-  const int k = min(kv[g], n);
+  const int k = min(min(kv[g], n), kmax);  // the output rows are kmax wide
   const uint16_t* S = scores + row * n;
   int* I = idx + row * kmax;
   float* V = val + row * kmax;

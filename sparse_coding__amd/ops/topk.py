@@ -15,6 +15,8 @@ def topk_select(scores: torch.Tensor, k: torch.Tensor, kmax: int, absolute: bool
     """Per-row top-k of ``scores`` [G, B, n] (fp32, or bf16) with per-model ``k`` (int32 [G]).
 
     Returns (idx int32 [G, B, kmax], val fp32 [G, B, kmax]); slots >= k[g] are (0, 0.0).
+    ``k[g]`` is clamped on the device to ``min(k[g], n, kmax)`` (the rows are kmax wide; the
+    decode, slot-list and scatter kernels clamp to kmax the same way).
     ``absolute`` selects by |score| (PCA-style) and keeps the signed value; ``relu``
     clamps kept values at 0 (TopKEncoder semantics).  ``out``: optional (idx, val) to fill
     (contiguous, e.g. a model slice of larger buffers).
