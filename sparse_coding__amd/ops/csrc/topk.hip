@@ -5,10 +5,17 @@
 // vmap over models because k changes the output shape (no_stacking=True,
 // big_sweep_experiments.py:246-253); here k lives in device memory and every
 // model runs in the same launches:
-//   topk_select_kernel   : exact per-row radix select (11/11/10-bit passes over the
-//                          orderable bit pattern, per-wave LDS histograms, parallel
-//                          digit search), scores kept in registers; emits (idx, value)
-//                          pairs in column order.
+//   select               : exact per-row top-k, (idx, value) pairs, four kernels by row format:
+//     topk_wave_kernel     fp32, n % 4 == 0, n <= 4096: a wave per row, bisection on the key
+//                          bits with the row in registers; output in column order.
+//     topk_block_kernel    fp32, n % 4 == 0, 4096 < n <= 16384: a block per row, bracketed
+//                          select (candidates compacted into LDS, thread-major output), full
+//                          bisection with column-order output on heavy ties or k > 256.
+//     topk_bf16_kernel     bf16 scores, n % 8 == 0, n <= 16384 (what training runs): the block
+//                          kernel on 16-bit keys; ambiguous ties re-ranked by exact fp32 scores.
+//     topk_select_kernel   fp32, every other n <= 16384 (n % 4 != 0): radix select (11/11/10-bit
+//                          passes, per-wave LDS histograms, parallel digit search), scores
+//                          kept in registers; thread-major output.
 //   topk_decode_grad     : one wave per row: sparse decode x_hat = sum_j v_j D[idx_j]
 //                          (bf16 dictionary gathered from L2), residual, per-row
 //                          squared error, then the k code gradients <R, D[idx_j]>
@@ -1305,6 +1312,9 @@ __global__ __launch_bounds__(256) void topk_scatter_kernel(const int* __restrict
 
 using namespace scamd;
 
+// 0 when the launches before it were accepted, 3 otherwise
+static int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
+
 extern "C" {
 
 int sc_topk_select(const float* scores, const int* k, int* idx, float* val, int G, int B, int n, int kmax,
@@ -1370,7 +1380,7 @@ int sc_topk_decode_grad(const int* idx, const float* val, const int* k, const vo
       reinterpret_cast<const uint16_t*>(D), reinterpret_cast<const uint16_t*>(X), sx, reinterpret_cast<uint16_t*>(R), \
       row_se, reinterpret_cast<uint16_t*>(codebuf), reinterpret_cast<uint16_t*>(dscbuf), G, B, n, d, kmax, dscv, prev_idx, \
       g_dense0); \
-    return hipGetLastError() == hipSuccess ? 0 : 3; }
+    return launched(); }
   SC_D(1) SC_D(2) SC_D(3) SC_D(4) SC_D(8) SC_D(16)
 #undef SC_D
   return 1;
@@ -1398,7 +1408,7 @@ int sc_topk_slot_lists(const int* idx, const int* k, int* cnt, int* offs, int* c
   } else {
     return 1;
   }
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return launched();
 }
 
 // G[0 .. Gs) rows of the weight gradient from the sorted slot lists (see the kernel).
@@ -1409,7 +1419,7 @@ int sc_topk_sparse_wgrad(const int* perm, const int* offs, const float* val, con
 #define SC_SW(V) \
   if (d == 256 * V) { hipLaunchKernelGGL((topk_sparse_wgrad_kernel<V>), grid, dim3(256), 0, stream, perm, offs, val, dscv, \
       reinterpret_cast<const uint16_t*>(R), reinterpret_cast<const uint16_t*>(X), sx, Gout, Gs, B, n, kmax, alpha, out_bf16); \
-    return hipGetLastError() == hipSuccess ? 0 : 3; }
+    return launched(); }
   SC_SW(1) SC_SW(2) SC_SW(3) SC_SW(4)
 #undef SC_SW
   return 1;
@@ -1420,14 +1430,14 @@ int sc_topk_scatter(const int* idx, const float* val, const int* k, void* code, 
   const long total = rows * kmax;
   hipLaunchKernelGGL(topk_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, idx, val, k,
                      reinterpret_cast<uint16_t*>(code), rows, rows_per_model, n, kmax);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return launched();
 }
 
 int sc_topk_clear(const int* idx, void* a, void* b, long rows, int n, int kmax, hipStream_t stream) {
   const long total = rows * kmax;
   hipLaunchKernelGGL(topk_clear_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, idx,
                      reinterpret_cast<uint16_t*>(a), reinterpret_cast<uint16_t*>(b), rows, n, kmax);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return launched();
 }
 
 }  // extern "C"
