@@ -966,6 +966,24 @@ class FusedSAEEnsemble:
             mx = torch.maximum(mx, part[:, :, 5].amax(1))
         return fs.FeatureStats(seen + N, acc[:, 0].round().to(torch.int64), acc[:, 1:].contiguous(), mx, tv, tr)
 
+    @torch.no_grad()
+    def atom_matches(self, m: int = 1):
+        """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` holding, for
+        every ordered pair (g, h), the ``m`` (1..8) nearest atoms of model h for each atom of model g (cosine
+        descending, lowest index among equal cosines), and for g == h the nearest *other* atoms.
+
+        Reads the bf16 shadow that holds the unit-norm dictionaries in place (the decoder shadow of untied
+        models, the encoder shadow of tied ones): the matches are those of the bf16-rounded dictionaries.
+        G launches of G problems per pass on the row-argmax epilogue of the grouped GEMM
+        (``ops.gemm.rowargmax_nt``).  Masked ensembles: atoms at or past ``dict_size[g]`` read (0.0, -1)
+        and are never a match.  Never synchronises; parameters, moments, shadows, counts, the step
+        counter and captured graphs are left as they are."""
+        from . import atom_match as am
+
+        if self.kind not in ("untied", "tied"):
+            raise NotImplementedError(f"atom_matches: no unit-norm dictionary shadow for {self.kind} SAEs")
+        return am.atom_matches_fused(self.dec_shadow, self.nactive, m)
+
     def feature_frequency(self) -> torch.Tensor:
         """Per-feature firing frequency [G, n] = feature_counts / rows_seen.  The counts are SAMPLED:
         the encoder epilogue accumulates them only on counting steps (every ``count_every``-th step, or

@@ -407,6 +407,17 @@ class FusedTopKEnsemble:
             tstats_ops.pick_stats(self._stat_lists, val, acc, mx, tv, tr, row_offset + i)
         return fs.FeatureStats(seen + N, acc[:, 0].round().to(torch.int64), acc[:, 1:].contiguous(), mx, tv, tr)
 
+    @torch.no_grad()
+    def atom_matches(self, m: int = 1):
+        """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` with the
+        SAE engine's contract (``m`` in 1..8; for g == h the nearest *other* atoms; lowest index among
+        equal cosines).  Reads the bf16 ``shadow`` of the unit-norm dictionaries in place; never
+        synchronises and leaves parameters, moments, shadows, window counts, the step counter and
+        captured graphs as they are."""
+        from . import atom_match as am
+
+        return am.atom_matches_fused(self.shadow, None, m)
+
     def state_dict(self):
         """Masters, moments and the step; with ``count_every > 0`` also the window counts."""
         sd = {"params": self.params, "m": self.m, "v": self.v, "step": self.step_count}

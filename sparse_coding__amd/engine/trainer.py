@@ -352,6 +352,33 @@ class EnsembleTrainer:
                      for i in range(0, rows.shape[0], self.batch_size))
             return fs.feature_stats_reference(codes, **kw)
 
+    # ------------------------------------------------------------------ nearest-atom matching
+    def atom_matches(self, m: int = 1):
+        """Nearest atoms across the models: an ``engine.atom_match.AtomMatches`` -- for every ordered pair
+        (g, h) the ``m`` nearest atoms of model h for each atom of model g, for g == h the nearest other
+        atoms; lowest index among equal cosines.
+
+        The fused SAE and top-k engines run their ``atom_matches`` on the bf16 shadows (under ensemble
+        sharding: this rank's models; graphed data-parallel replicas: the local engine, the models are
+        the same on every rank).  The analytic and eager engines with an SAE or top-k signature run the
+        fp64 oracle on their unstacked fp32 dictionaries.  Every other kind (the unrolled and
+        FISTA-in-the-loss engines) raises ``NotImplementedError``."""
+        from . import atom_match as am
+
+        if self.kind in ("fused-sae", "fused-topk") or self.kind.endswith("-graphed"):
+            return self.impl.atom_matches(m)
+        sae = self.sig in analytic._KINDS or self.sig is TopKEncoder
+        if not (self.kind in ("analytic", "eager") or self.kind.endswith("-eager")) or not sae:
+            raise NotImplementedError(f"atom_matches: no unit-norm dictionary to match for the {self.kind} engine "
+                                      f"with {getattr(self.sig, '__name__', self.sig)}")
+        with torch.no_grad():
+            dicts = [ld.get_learned_dict().detach().float() for ld in self.impl.to_learned_dicts(self.device)]
+        n = max(D.shape[0] for D in dicts)
+        stacked = torch.zeros(len(dicts), n, dicts[0].shape[1], device=dicts[0].device)
+        for g, D in enumerate(dicts):
+            stacked[g, :D.shape[0]] = D
+        return am.atom_matches_reference(stacked, [D.shape[0] for D in dicts], m, True)
+
     # ------------------------------------------------------------------ export / state
     def hyperparams(self, ensemble_hyperparams: Sequence[str] = (), buffer_hyperparams: Sequence[str] = ("l1_alpha",),
                     local: bool = False) -> List[dict]:

@@ -64,6 +64,33 @@ def run_mmcs_with_larger(learned_dicts: Sequence[Sequence[torch.Tensor]], thresh
     return av, above, full
 
 
+def nearest_max_cosine(small: torch.Tensor, large: torch.Tensor, fused: Optional[bool] = None
+                       ) -> Tuple[np.ndarray, np.ndarray]:
+    """(cosine, index) of each atom of ``small`` with its nearest atom of ``large`` (many-to-one; the lowest
+    index among equal cosines) -- ``eval.metrics.nearest_atoms``: no [n1, n2] matrix on the host."""
+    cos, idx = M.nearest_atoms(_unit(small.float()), _unit(large.float().to(small.device)), fused=fused)
+    return cos[:, 0].double().cpu().numpy(), idx[:, 0].cpu().numpy()
+
+
+def nearest_with_larger(learned_dicts: Sequence[Sequence[torch.Tensor]], threshold: float = 0.9):
+    """``run_mmcs_with_larger`` from nearest atoms instead of the Hungarian assignment:
+    ``learned_dicts[l1][size]`` -> (mean nearest cosine [L, S], % atoms above threshold [L, S], per-cell
+    similarity arrays [L][S-1], per-cell index arrays [L][S-1]: the matched atom of the next larger
+    dictionary)."""
+    L, S = len(learned_dicts), len(learned_dicts[0])
+    av = np.zeros((L, S))
+    above = np.zeros((L, S))
+    full = [[None] * (S - 1) for _ in range(L)]
+    matched = [[None] * (S - 1) for _ in range(L)]
+    for i in range(L):
+        for j in range(S - 1):
+            sims, idx = nearest_max_cosine(learned_dicts[i][j], learned_dicts[i][j + 1])
+            av[i, j] = sims.mean()
+            above[i, j] = (sims > threshold).mean() * 100
+            full[i][j], matched[i][j] = sims, idx
+    return av, above, full, matched
+
+
 def effective_number_of_neurons(features: torch.Tensor) -> torch.Tensor:
     p = features.abs() / features.abs().sum(dim=1, keepdim=True)
     return 1.0 / p.pow(2).sum(dim=1)
@@ -74,9 +101,15 @@ def feature_entropy(features: torch.Tensor) -> torch.Tensor:
     return -(p * torch.log(p + 1e-8)).sum(dim=1)
 
 
-def converged_feature_stats(small: torch.Tensor, large: torch.Tensor, threshold: float = 0.9) -> Dict[str, float]:
-    """ENN / entropy of atoms that reappear in the larger dictionary vs those that do not."""
-    sims = torch.as_tensor(hungarian_max_cosine(small, large))
+def converged_feature_stats(small: torch.Tensor, large: torch.Tensor, threshold: float = 0.9,
+                            matching: str = "hungarian") -> Dict[str, float]:
+    """ENN / entropy of atoms that reappear in the larger dictionary vs those that do not.  ``matching``:
+    "hungarian" (one-to-one assignment on the host) or "nearest" (each atom's nearest atom of ``large``,
+    ``nearest_max_cosine``)."""
+    if matching not in ("hungarian", "nearest"):
+        raise ValueError(f"matching must be 'hungarian' or 'nearest', got {matching!r}")
+    sims = torch.as_tensor(hungarian_max_cosine(small, large) if matching == "hungarian"
+                           else nearest_max_cosine(small, large)[0])
     conv = sims > threshold
     enn = effective_number_of_neurons(small.float().cpu())
     ent = feature_entropy(small.float().cpu())

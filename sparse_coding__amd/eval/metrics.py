@@ -96,6 +96,68 @@ def max_cosine(rows: torch.Tensor, against: torch.Tensor, fused: bool | None = N
     return (rows @ against.T).max(dim=-1).values
 
 
+def nearest_atoms(rows: torch.Tensor, against: torch.Tensor, m: int = 1, exclude_self: bool = False,
+                  fused: bool | None = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ``m`` (1..8) nearest atoms of ``against`` [n2, d] for every atom of ``rows`` [n1, d] (inputs
+    already unit-norm): (cos fp32 [n1, m], idx int64 [n1, m]), cosine descending; among equal cosines the
+    lowest index wins; slots without a candidate read (0.0, -1).  ``exclude_self`` (``rows`` and
+    ``against`` the same dictionary): atom i is not its own match.
+
+    ``fused=None`` follows ``max_cosine``: on the GPU from ``ROWMAX_MIN_ENTRIES`` similarity entries on, the
+    row-argmax kernel (``ops.gemm.rowargmax_nt``: bf16 MFMA, the matches of the bf16-rounded dictionaries,
+    the [n1, n2] matrix never materialised); otherwise the exact fp32 torch product, same tie rule."""
+    m = int(m)
+    if not 1 <= m <= 8:
+        raise ValueError(f"m must be in [1, 8], got {m}")
+    n1, n2 = rows.shape[0], against.shape[0]
+    if exclude_self and n1 != n2:
+        raise ValueError(f"exclude_self needs the same dictionary on both sides, got {n1} and {n2} atoms")
+    if fused is None:
+        fused = rows.is_cuda and n1 * n2 >= ROWMAX_MIN_ENTRIES
+    if fused:
+        from ..ops import gemm
+
+        cos, idx = gemm.rowargmax_nt(rows.to(torch.bfloat16).contiguous(), against.to(torch.bfloat16).contiguous(),
+                                     m=m, exclude_self=exclude_self)
+        return cos, idx.long()
+    sim = rows.float() @ against.float().T
+    ar = torch.arange(n2, device=sim.device)
+    if exclude_self:
+        sim.fill_diagonal_(float("-inf"))
+    cos = torch.zeros(n1, m, device=sim.device)
+    idx = torch.full((n1, m), -1, dtype=torch.int64, device=sim.device)
+    for k in range(min(m, n2)):
+        mx = sim.max(dim=-1).values
+        col = torch.where(sim == mx.unsqueeze(1), ar, n2).amin(dim=-1)  # the lowest index among equal values
+        found = mx > float("-inf")
+        cos[:, k] = torch.where(found, mx, torch.zeros_like(mx))
+        idx[:, k] = torch.where(found, col, torch.full_like(col, -1))
+        sim.scatter_(1, col.clamp(max=n2 - 1).unsqueeze(1), float("-inf"))
+    return cos, idx
+
+
+def mutual_nearest(a: torch.Tensor, b: torch.Tensor, fused: bool | None = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The pairs (i, j) with b_j the nearest atom of a_i and a_i the nearest atom of b_j: (ia, ib, cos),
+    one-to-one by construction and ordered by ``ia``; ``cos`` is <a_i, b_j> as seen from ``a``."""
+    ca, ab = nearest_atoms(a, b, fused=fused)
+    _, ba = nearest_atoms(b, a, fused=fused)
+    ab, ba = ab[:, 0], ba[:, 0]
+    ia = torch.arange(a.shape[0], device=ab.device)
+    keep = (ab >= 0) & (ba[ab.clamp(min=0)] == ia)
+    return ia[keep], ab[keep], ca[keep, 0]
+
+
+def duplicate_atoms(rows: torch.Tensor, threshold: float = 0.9, fused: bool | None = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Atoms whose nearest *other* atom of the same dictionary is at or above ``threshold``: (i, j, cos)
+    with j the nearest other atom of atom i, ordered by i."""
+    cos, idx = nearest_atoms(rows, rows, exclude_self=True, fused=fused)
+    cos, idx = cos[:, 0], idx[:, 0]
+    keep = (idx >= 0) & (cos >= threshold)
+    return torch.arange(rows.shape[0], device=idx.device)[keep], idx[keep], cos[keep]
+
+
 def mcs_duplicates(ground: LearnedDict, model: LearnedDict) -> torch.Tensor:
     """Max cosine similarity of each ``model`` atom to the ``ground`` atoms (reference :268-272)."""
     return max_cosine(model.get_learned_dict(), ground.get_learned_dict())

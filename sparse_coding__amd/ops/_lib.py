@@ -58,6 +58,8 @@ def signatures():
                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
         "sc_col_moments": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
         "sc_col_topk": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p],
+        "sc_rowmatch_reduce": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_int, c_int,
+                               c_void_p, c_long, c_int, c_int, c_void_p, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -24,7 +24,7 @@ constexpr int PT = 128;
 // (5 was EPI_ADAM, Adam fused into the weight-gradient epilogue: measured slower than the
 // separate streaming Adam kernel and removed)
 enum { EPI_ENC = 0, EPI_DEC = 1, EPI_DC = 2, EPI_F32 = 3, EPI_BF16 = 4, EPI_ENC_CNT = 6,
-       EPI_DC_MASK = 7, EPI_ENC_ACT = 8, EPI_DC_ACT = 9, EPI_ROWMAX = 10 };
+       EPI_DC_MASK = 7, EPI_ENC_ACT = 8, EPI_DC_ACT = 9, EPI_ROWMAX = 10, EPI_ROWARGMAX = 11 };
 
 // Activity bitmask of the codes: see mask_bit() in sae_gemm_kernel.h (one 64-bit word per lane
 // per 64x64 block, written by the encoder epilogue, read by the code-gradient epilogue instead
@@ -70,7 +70,7 @@ struct GemmParams {
   const float* bias;  // ENC: [G][N] fp32
   long sbias;
   const int* nactive;  // ENC: per-group number of live columns (masked SAEs), may be null
-  const uint16_t* aux; // DEC: x (bf16); DC: c (bf16)
+  const uint16_t* aux; // DEC: x (bf16); DC: c (bf16); ROWARGMAX: int32 exclusion lists [G][M][ldaux], may be null
   long ldaux, saux;
   float* part;         // per-block scalar partials [G][tiles] x nstat
   float* colpart;      // per-(tile_m, column) partials [G][tiles_m][N] (DC: bias grad, ENC: counts)

@@ -47,6 +47,7 @@ int sc_gemm(int epi, int layout, int nprob, int M, int N, int K1, int K2, int G,
   if ((epi == EPI_DC_MASK || epi == EPI_DC_ACT) && !cmask) return 4;
   if (epi == EPI_DC_ACT && (!aux || !colpart || !l1)) return 4;
   if ((epi == EPI_ENC_ACT || epi == EPI_DC_ACT) && (act < 0 || act > 2 || (act == 2 && !ascale))) return 4;
+  if (epi == EPI_ROWARGMAX && aux && (ldaux < 1 || ldaux > 8)) return 4;
   if (ksplit < 1 || ksplit > (K1 + K2) / 64 || (ksplit > 1 && epi != EPI_F32 && epi != EPI_BF16)) return 7;
   GemmParams p;
   for (int i = 0; i < nprob; ++i) {
@@ -70,7 +71,7 @@ int sc_gemm(int epi, int layout, int nprob, int M, int N, int K1, int K2, int G,
   p.cmask2 = reinterpret_cast<uint64_t*>(cmask2); p.rcol = rcol;
   p.nact_m = nact_m; p.nact_k = nact_k;
   // written-through stores address one model's output with 32-bit byte offsets: plain stores beyond that
-  const long esz = (epi == EPI_F32 || epi == EPI_ROWMAX) ? 4 : 2;
+  const long esz = (epi == EPI_F32 || epi == EPI_ROWMAX || epi == EPI_ROWARGMAX) ? 4 : 2;
   p.store_wt = store_wt != 0 && ((long)(M - 1) * ldc + N) * esz < 0x7FFFFFFFl;
   // masked launches with host copies of the live sizes launch only their live tiles
   p.want_comp = nact_host != nullptr && G <= 16;

@@ -21,6 +21,9 @@
 //             s^2 thr((pre)/s^2), thr(u) = relu6(60(u - 0.9))/6 + relu(u - 1) (:254-257)
 //   EPI_ROWMAX: per-row max of alpha * A B^T over column tiles (max cosine similarity /
 //             MMCS, standard_metrics.py:268-301) -- the [M, N] product never reaches HBM
+//   EPI_ROWARGMAX: EPI_ROWMAX with the column of the max (nearest-atom matching): (value, column)
+//             pairs per 64-column wave tile, lowest column among equal values; optional live
+//             columns (nactive) and per-row exclusion lists (aux); csrc/atom_match.hip reduces them
 //
 // Tiling (template "shape"): a WGM x WGN grid of waves, each owning a
 // (16 WI) x (16 WJ) sub-tile = WI x WJ v_mfma_f32_16x16x32_bf16 accumulators:
@@ -172,7 +175,7 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
   // launch asks for it (GemmParams::store_wt; block-uniform), so that the release at the end of the
   // kernel finds the tile already out of the L2.  The written-through form addresses this model's
   // output through a buffer resource with 32-bit byte offsets (the host keeps it off for larger spans).
-  constexpr int ESZ = (EPI == EPI_F32 || EPI == EPI_ROWMAX) ? 4 : 2;
+  constexpr int ESZ = (EPI == EPI_F32 || EPI == EPI_ROWMAX || EPI == EPI_ROWARGMAX) ? 4 : 2;
   const bool wt = WTC && p.store_wt != 0;  // (WTC false: an instantiation that keeps plain stores, see gemm_block)
   char* const Cg = reinterpret_cast<char*>(cptr) + (long)g * p.sc * ESZ;  // this model's output
   const rsrc_t crs = store_rsrc(Cg);
@@ -643,6 +646,75 @@ __device__ __forceinline__ void sae_epilogue(const GemmParams& p, f32x4_t (&acc)
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
       if (lane < 16) C[(long)(rowb + i * 16) * ldp + tn * WGN + wc] = mx;
+    }
+    return;
+  }
+  if constexpr (EPI == EPI_ROWARGMAX) {
+    // EPI_ROWMAX with the column of the max: per (row, wave column) the pair (max of alpha * acc,
+    // global column of that max) as two fp32 words (the column bit-cast) at
+    // C[g][row][tn * WGN + wc][2].  Among equal values the lowest column wins: a lane takes the max of
+    // its 16 values as EPI_ROWMAX does (the same fmaxf chain, so the same bits), then the lowest of its
+    // columns that holds it (walked downwards, the last hit stays); across the four 16-lane groups of a
+    // row the pair is compared by value, then by column.  Columns >= nactive[g] and columns named in
+    // the row's exclusion list (aux as int32 [G][M][ldaux], ldaux <= 8, -1 = unused slot) take no part:
+    // they carry -3.0e38, EPI_ROWMAX's initial value, below every product of finite inputs.  A tile with no
+    // candidate writes (-3.0e38, INT_MAX), which loses to every real column.
+    float* C = reinterpret_cast<float*>(cptr) + (long)g * p.sc;
+    const long ldp = (long)tiles_n * WGN;
+    constexpr int NONE = 0x7fffffff;
+    constexpr float LOW = -3.0e38f;
+    const int wcol0 = n0 + wc * (WJ * 16);                          // this wave's first column
+    const int nlive = (p.nactive ? p.nactive[g] : NONE) - colb;      // live columns from this lane's first
+    const int* X = p.aux ? reinterpret_cast<const int*>(p.aux) + (long)g * p.saux : nullptr;
+    const int E = (int)p.ldaux;
+    const bool masked = X != nullptr || p.nactive != nullptr;        // (block-uniform)
+#pragma unroll
+    for (int i = 0; i < WI; ++i) {
+      float v[WJ][4];
+#pragma unroll
+      for (int j = 0; j < WJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[j][r] = alpha * acc[i][j][r];
+      if (masked) {
+        // bit j * 4 + r: column colb + 16 j + r is excluded for this row
+        uint32_t ex = 0;
+        if (X) {
+          const int* xr = X + (long)(rowb + i * 16) * E;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            if (e < E) {
+              const uint32_t rel = (uint32_t)(xr[e] - wcol0);
+              if (rel < (uint32_t)(WJ * 16) && ((rel >> 2) & 3) == (uint32_t)(lane >> 4))
+                ex |= 1u << ((rel >> 4) * 4 + (rel & 3));
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < WJ; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (j * 16 + r >= nlive || ((ex >> (j * 4 + r)) & 1u)) v[j][r] = LOW;
+      }
+      float mx = LOW;
+#pragma unroll
+      for (int j = 0; j < WJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, v[j][r]);
+      int rel = 0;
+#pragma unroll
+      for (int j = WJ - 1; j >= 0; --j)
+#pragma unroll
+        for (int r = 3; r >= 0; --r) rel = v[j][r] == mx ? j * 16 + r : rel;
+      int col = mx > LOW ? colb + rel : NONE;
+#pragma unroll
+      for (int s = 16; s <= 32; s <<= 1) {
+        const float ov = __shfl_xor(mx, s);
+        const int oc = __shfl_xor(col, s);
+        if (ov > mx || (ov == mx && oc < col)) { mx = ov; col = oc; }
+      }
+      if (lane < 16)
+        *reinterpret_cast<float2*>(C + ((long)(rowb + i * 16) * ldp + tn * WGN + wc) * 2) =
+            make_float2(mx, __int_as_float(col));
     }
     return;
   }
@@ -1132,6 +1204,9 @@ int launch(int epi, bool ak, bool bk, GemmParams p, int nprob, hipStream_t strea
       break;
     case EPI_ROWMAX:
       if constexpr (FULL) { if (!(ak && bk)) return 5; SC_L(true, true, EPI_ROWMAX); }
+      break;
+    case EPI_ROWARGMAX:
+      if constexpr (FULL) { if (!(ak && bk)) return 5; SC_L(true, true, EPI_ROWARGMAX); }
       break;
     case EPI_F32:
       if constexpr (FULL) {

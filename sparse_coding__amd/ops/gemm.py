@@ -17,7 +17,7 @@ import torch
 from . import _lib, store_policy
 
 EPI_ENC, EPI_DEC, EPI_DC, EPI_F32, EPI_BF16, EPI_ENC_CNT, EPI_DC_MASK = 0, 1, 2, 3, 4, 6, 7
-EPI_ENC_ACT, EPI_DC_ACT, EPI_ROWMAX = 8, 9, 10
+EPI_ENC_ACT, EPI_DC_ACT, EPI_ROWMAX, EPI_ROWARGMAX = 8, 9, 10, 11
 # code activations of the ENC_ACT / DC_ACT epilogues
 ACT_RELU, ACT_REVERSE, ACT_THRESHOLD = 0, 1, 2
 TILE_M, TILE_N, TILE_K = 128, 128, 64
@@ -48,7 +48,7 @@ TILE_M, TILE_N, TILE_K = 128, 128, 64
 # counting encoder (its epilogue spills at 128 VGPRs: slower), the decoder (slower) or masked-ensemble
 # launches (nactive / nact_k: they fall back to cfg 29 below).
 _CFG_DEFAULT = {EPI_ENC: 14, EPI_DEC: 1, EPI_DC: 1, EPI_F32: 0, EPI_BF16: 0, EPI_ENC_CNT: 29,
-                EPI_DC_MASK: 14, EPI_ENC_ACT: 1, EPI_DC_ACT: 1, EPI_ROWMAX: 1}
+                EPI_DC_MASK: 14, EPI_ENC_ACT: 1, EPI_DC_ACT: 1, EPI_ROWMAX: 1, EPI_ROWARGMAX: 1}
 _CFG_FALLBACK = {14: 29}  # 256x128 eight-wave default -> the 128x128 pipelined BK32 x 3 ring (M % 256 != 0)
 _CFG_OVERRIDE = None
 # (epi, operand layout) -> cfg: overrides _CFG_DEFAULT for that layout only.  The bf16-out GEMMs of the
@@ -177,7 +177,7 @@ def _launch(epi, layout, M, N, K1, K2, G, a_ops, b_ops, outs, alphas, ldc, sc, *
     # host copy of a masked ensemble's live sizes: the launcher then launches only live tiles
     nh = (C.c_int * len(nact_host))(*[int(v) for v in nact_host]) if nact_host is not None else None
     # output tiles written through the L2 (ops/store_policy.py), while one model's output is addressable
-    esize = 4 if epi in (EPI_F32, EPI_ROWMAX) else 2
+    esize = 4 if epi in (EPI_F32, EPI_ROWMAX, EPI_ROWARGMAX) else 2
     store_wt = store_policy.gemm_write_through(epi, store_policy.output_span_bytes(M, N, ldc, esize))
     rc = _lib.lib().sc_gemm(
         epi, layout, nprob, M, N, K1, K2, G, A, Bo, Cp, al, ldc, sc,
@@ -430,6 +430,108 @@ def rowmax_nt(a, b, alpha=1.0, cfg=None):
             [float(alpha)], tiles, Mp * tiles, cfg=cfg)
     out = part.amax(dim=-1)[:, :M]
     return out[0] if squeeze else out
+
+
+MAX_MATCHES = 8  # slots of a row's exclusion list (csrc/sae_gemm_kernel.h, EPI_ROWARGMAX)
+
+
+def _live_tensor(live, G, hi, device):
+    """Per-model live extents (sequence of ints or an int32 / int64 tensor [G]) as int32 [G] on ``device``,
+    clamped to ``hi`` -- no synchronisation when a device tensor comes in."""
+    if live is None:
+        return None
+    t = torch.as_tensor(live, device=device).to(torch.int32).reshape(-1)
+    _need(t.numel() == G, f"live extents: {t.numel()} values for {G} models")
+    return t.clamp(min=0, max=hi).contiguous()
+
+
+def rowargmax_nt(a, b, alpha=1.0, cfg=None, m=1, exclude_self=False, live_cols=None, live_rows=None,
+                 exclude=None, out=None):
+    """The ``m`` largest alpha <a[g, i], b[g, j]> of every row i and their columns j:
+    [G, M, K] x [G, N, K] (or one shared [N, K]) -> (val fp32 [G, M, m], idx int32 [G, M, m]), ordered by
+    value descending, then column ascending; among equal values the lowest column always wins.  The 2-D
+    form drops G.  Rows with fewer than ``m`` candidates end in (0.0, -1) slots.
+
+    Nearest-atom matching: the EPI_ROWARGMAX epilogue keeps (max, column) per 64-column
+    wave tile, ``sc_rowmatch_reduce`` (csrc/atom_match.hip) folds the tiles; pass k excludes the winners
+    of passes < k through a per-row exclusion list the reduction fills, all on the stream.
+    ``exclude_self`` (M == N): column i takes no part for row i.  ``exclude``: int32 [G, M, E] columns
+    that take no part for that row (-1 = unused slot).  ``live_cols`` / ``live_rows`` ([G] ints or a
+    device tensor): columns past a model's live count take no part, rows past it read (0.0, -1).
+    Padding as in ``rowmax_nt`` (extra columns repeat b's first row and lose to it -- with exclusions,
+    where column 0 may be out, they are dead columns; K zero-padded);
+    operands that already tile and are contiguous bf16 are read in place.  ``out``: (val, idx) views to
+    write into ([G, M, m], unit stride over m, row stride m).
+    """
+    squeeze = a.dim() == 2
+    if squeeze:
+        a = a.unsqueeze(0)
+    G, M, K = a.shape
+    shared = b.dim() == 2
+    N = b.shape[-2]
+    _need(b.shape[-1] == K and (shared or b.shape[0] == G), f"shapes {tuple(a.shape)} x {tuple(b.shape)}")
+    _need(a.is_cuda and b.is_cuda, "rowargmax_nt runs on the GPU")
+    m = int(m)
+    _need(1 <= m <= MAX_MATCHES, f"m = {m} must lie in 1..{MAX_MATCHES}")
+    _need(not exclude_self or M == N, "exclude_self needs M == N")
+    if cfg is None:
+        cfg = 3 if M * N >= (1 << 24) else 1
+    _need(cfg in (1, 2, 3), "rowargmax_nt: cfg 1 (128x128), 2 (256x128) or 3 (256x256 blocks)")
+    bm, bn = SHAPES[cfg]
+    Mp, Np, Kp = -(-M // bm) * bm, -(-N // bn) * bn, -(-K // 64) * 64
+    bf, dev = torch.bfloat16, a.device
+    if (Mp, Kp) != (M, K) or a.dtype != bf or not a.is_contiguous():
+        ap = torch.zeros(G, Mp, Kp, device=dev, dtype=bf)
+        ap[:, :M, :K] = a
+    else:
+        ap = a
+    if (Np, Kp) != (N, K) or b.dtype != bf or not b.is_contiguous():
+        bp = torch.zeros(*b.shape[:-2], Np, Kp, device=dev, dtype=bf)
+        bp[..., :N, :K] = b
+        if Np > N:
+            bp[..., N:, :K] = b[..., :1, :]
+    else:
+        bp = b
+    nactive = _live_tensor(live_cols, G, N, dev)
+    nact_m = _live_tensor(live_rows, G, M, dev)
+    # the exclusion list: the caller's columns, the row itself, then the winners of the earlier passes
+    e_user = 0 if exclude is None else int(exclude.shape[-1])
+    e0 = e_user + int(bool(exclude_self))
+    E = e0 + m - 1
+    _need(E <= MAX_MATCHES, f"exclusion slots {e0} + passes {m} - 1 exceed {MAX_MATCHES}")
+    excl = None
+    if E and Np > N and nactive is None:
+        # a padded copy of column 0 loses to column 0 only while column 0 takes part: with exclusions
+        # the padding is kept out as dead columns instead
+        nactive = torch.full((G,), N, device=dev, dtype=torch.int32)
+    if E:
+        excl = torch.full((G, Mp, E), -1, device=dev, dtype=torch.int32)
+        if e_user:
+            _need(tuple(exclude.shape) == (G, M, e_user), f"exclude must be [G, M, E], got {tuple(exclude.shape)}")
+            excl[:, :M, :e_user] = exclude.to(device=dev, dtype=torch.int32)
+        if exclude_self:
+            excl[:, :, e_user] = torch.arange(Mp, device=dev, dtype=torch.int32)
+    if out is None:
+        val = torch.empty(G, M, m, device=dev, dtype=torch.float32)
+        idx = torch.empty(G, M, m, device=dev, dtype=torch.int32)
+    else:
+        val, idx = out
+        for t, dt in ((val, torch.float32), (idx, torch.int32)):
+            _need(t.dtype == dt and tuple(t.shape) == (G, M, m) and t.stride(-1) == 1 and t.stride(-2) == m
+                  and t.stride(0) >= M * m and t.is_cuda, "out: (fp32, int32) [G, M, m] with rows of m contiguous")
+        _need(val.stride(0) == idx.stride(0), "out: val and idx must share their group stride")
+    tiles = Np // 64  # one (value, column) pair per row and 64-column wave tile
+    part = torch.empty(G, Mp, tiles, 2, device=dev, dtype=torch.float32)
+    a_ops = [_op(ap, Kp, Mp * Kp)] * 2
+    b_ops = [_op(bp, Kp, 0 if shared else Np * Kp)] * 2
+    for k in range(m):
+        _launch(EPI_ROWARGMAX, 3, Mp, Np, Kp, 0, G, a_ops, b_ops, [part], [float(alpha)], 2 * tiles,
+                Mp * tiles * 2, cfg=cfg, nactive=nactive, aux=excl, ldaux=E, saux=Mp * E)
+        rc = _lib.lib().sc_rowmatch_reduce(
+            _lib.ptr(part), G, Mp, tiles, M, _lib.ptr(val), _lib.ptr(idx), val.stride(0), m, k,
+            _lib.ptr(excl), Mp * E, E, e0, _lib.ptr(nact_m), _lib.stream_handle())
+        _lib.check(rc, "sc_rowmatch_reduce")
+    return (val[0], idx[0]) if squeeze else (val, idx)
 
 
 def matmul_nt(a, b, out, alpha=1.0):
