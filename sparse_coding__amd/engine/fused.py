@@ -967,6 +967,57 @@ class FusedSAEEnsemble:
         return fs.FeatureStats(seen + N, acc[:, 0].round().to(torch.int64), acc[:, 1:].contiguous(), mx, tv, tr)
 
     @torch.no_grad()
+    def encode_sparse(self, rows: torch.Tensor, *, budget: Optional[int] = None):
+        """The codes of every model on ``rows`` [N, d] (N a positive multiple of the batch size) as an
+        ``engine.sparse_codes.SparseCodes``: per-model CSR of the strictly positive bf16 codes, columns
+        ascending within a row, values widened to fp32.
+
+        Per batch: the encoder launch alone (as ``feature_stats``: the scratch buffers ``c`` / ``cmask`` /
+        ``enc_part`` are overwritten; no decoder), then ``code_row_counts``, a device-side cumsum into the
+        row pointers and ``code_compact`` (``csrc/sparse_codes.hip``).  ``budget=int``: buffers of
+        ``min(N * budget, N * n)`` entries per model, one sweep, never synchronises; a model with more
+        entries keeps the prefix that fits, ``row_ptr`` still carries its true counts and ``overflow()`` /
+        ``check()`` report it.  ``budget=None`` (default): a count-only sweep over the pool, ONE
+        synchronisation to read the per-model totals, then the fill sweep (the pool is encoded twice) into
+        buffers sized to the largest model.  Tied models with a fixed affine centering: the codes of the
+        centred rows, as ``feature_stats``.  Masked ensembles: columns at or past ``dict_size[g]`` are zero
+        codes and never appear.  Bit-reproducible.  Parameters, moments, shadows, ``feature_counts``,
+        ``rows_seen``, the step counter and captured graphs are left as they are."""
+        from ..ops import sparse_codes as sc_ops
+        from . import sparse_codes as sc
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"encode_sparse: {why}")
+        B, G, n, d = self.batch_size, self.n_models, self.n, self.d
+        if rows.dim() != 2 or rows.shape[1] != d:
+            raise ValueError(f"rows must be [N, {d}], got {tuple(rows.shape)}")
+        N = rows.shape[0]
+        if N <= 0 or N % B:
+            raise ValueError(f"encode_sparse needs a positive multiple of the batch size ({B}) rows, got {N}")
+        cap = sc.check_budget(budget, N, n)
+        dev = self.device
+        pool = self._x_bf16(rows)
+        nnz = torch.empty(G, B, device=dev, dtype=torch.int32)
+        row_ptr = torch.zeros(G, N + 1, device=dev, dtype=torch.int64)
+        if cap is None:
+            for i in range(0, N, B):
+                self._encode_only(self.prepare(pool[i:i + B]))
+                sc_ops.code_row_counts(self.c, nnz)
+                sc_ops.extend_row_ptr(row_ptr, nnz, i)
+            cap = int(row_ptr[:, -1].max())  # the one synchronisation
+        col = torch.zeros(G, cap, device=dev, dtype=torch.int32)
+        val = torch.zeros(G, cap, device=dev, dtype=torch.float32)
+        counted = budget is None
+        for i in range(0, N, B):
+            self._encode_only(self.prepare(pool[i:i + B]))
+            if not counted:
+                sc_ops.code_row_counts(self.c, nnz)
+                sc_ops.extend_row_ptr(row_ptr, nnz, i)
+            sc_ops.code_compact(self.c, row_ptr, col, val, i)
+        return sc.SparseCodes(N, n, row_ptr, col, val)
+
+    @torch.no_grad()
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` holding, for
         every ordered pair (g, h), the ``m`` (1..8) nearest atoms of model h for each atom of model g (cosine

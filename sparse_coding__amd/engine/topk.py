@@ -408,6 +408,33 @@ class FusedTopKEnsemble:
         return fs.FeatureStats(seen + N, acc[:, 0].round().to(torch.int64), acc[:, 1:].contiguous(), mx, tv, tr)
 
     @torch.no_grad()
+    def encode_sparse(self, rows: torch.Tensor, *, budget: Optional[int] = None):
+        """The codes of every model on ``rows`` [N, d] (N a positive multiple of the batch size) as an
+        ``engine.sparse_codes.SparseCodes`` with the SAE engine's contract: per-model CSR of the picks
+        with a positive code (a pick the ReLU clamped to 0 is no entry), columns ascending within a row.
+
+        Per batch: the forward-only select (no decode); the kept picks of each row are sorted by column
+        with torch ops on the [G, B, kmax] pick buffers -- no dense code matrix, no new kernel.
+        ``budget=int``: buffers of ``min(N * budget, N * n)`` entries per model, never synchronises,
+        overflow is reported through ``row_ptr`` / ``overflow()``.  ``budget=None`` (default): ONE
+        synchronisation reads the per-model totals and the buffers are sized to the largest model.
+        Equals the oracle on ``engine.topk_stats.dense_codes_from_picks`` of the same picks.  Parameters,
+        moments, shadows, window counts, the step counter and captured graphs are left as they are."""
+        from . import sparse_codes as sc
+
+        N = self._check_rows(rows, "encode_sparse")
+        B = self.batch_size
+        cap = sc.check_budget(budget, N, self.n)
+        pool = self._x_bf16(rows)
+
+        def picks():
+            for i in range(0, N, B):
+                idx, val = self._forward_only(pool[i:i + B], decode=False)
+                yield idx, val  # (consumed before the next batch overwrites the pick buffers)
+
+        return sc.sparse_codes_from_picks(picks(), self.k, self.n, cap)
+
+    @torch.no_grad()
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` with the
         SAE engine's contract (``m`` in 1..8; for g == h the nearest *other* atoms; lowest index among

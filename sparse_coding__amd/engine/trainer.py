@@ -352,6 +352,42 @@ class EnsembleTrainer:
                      for i in range(0, rows.shape[0], self.batch_size))
             return fs.feature_stats_reference(codes, **kw)
 
+    # ------------------------------------------------------------------ sparse codes
+    def encode_sparse(self, rows: torch.Tensor, **kw):
+        """The codes of every model on ``rows`` [N, d] as an ``engine.sparse_codes.SparseCodes``: per-model
+        CSR of the strictly positive codes (keyword ``budget``: entries per row the buffers hold, or
+        ``None`` to size them exactly with one synchronisation).
+
+        The fused SAE and top-k engines run their ``encode_sparse`` (N a multiple of the batch size; under
+        ensemble sharding each rank gets the codes of its own models on the rows it is given, N a multiple
+        of the engine's global batch).  The analytic and eager engines with an untied / tied SAE signature
+        run the oracle on their fp32 torch codes, ``batch_size`` rows at a time.  Data-parallel trainers
+        and every other kind (top-k under the eager engine included) raise ``NotImplementedError``."""
+        from . import feature_stats as fs
+        from . import sparse_codes as sc
+
+        if self.dp is not None:
+            raise NotImplementedError("encode_sparse: data-parallel replicas (parallel='dp'/'zero1') hold the same "
+                                      "models on different rows; encode on one rank's engine")
+        if self.kind in ("fused-sae", "fused-topk"):
+            return self.impl.encode_sparse(rows.to(self.device), **kw)
+        kind = analytic._KINDS.get(self.sig)
+        if self.kind not in ("analytic", "eager") or kind is None:
+            raise NotImplementedError(f"encode_sparse: no code path for the {self.kind} engine with "
+                                      f"{getattr(self.sig, '__name__', self.sig)}")
+        impl = self.impl
+        n, d = impl.params["encoder"].shape[-2:]
+        if rows.dim() != 2 or rows.shape[1] != d or rows.shape[0] < 1:
+            raise ValueError(f"rows must be [N, {d}] with N >= 1, got {tuple(rows.shape)}")
+        cap = sc.check_budget(kw.pop("budget", None), rows.shape[0], n)
+        if kw:
+            raise TypeError(f"encode_sparse: unexpected keywords {sorted(kw)}")
+        buffers = getattr(impl, "buffers", {})
+        with torch.no_grad():
+            codes = (fs.stacked_codes(impl.params, buffers, kind, rows[i:i + self.batch_size])
+                     for i in range(0, rows.shape[0], self.batch_size))
+            return sc.sparse_codes_reference(codes, cap)
+
     # ------------------------------------------------------------------ nearest-atom matching
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models: an ``engine.atom_match.AtomMatches`` -- for every ordered pair

@@ -124,6 +124,64 @@ def make_feature_activation_dataset(lm: HookedLM, learned_dict, layer: int, laye
     return FeatureActivationDataset(fragments.to(torch.int32).cpu(), acts, maxes, strs)
 
 
+def feature_activation_dataset_from_sparse(sc, g: int, fragments: torch.Tensor, max_features: int = 0,
+                                           token_strs: Optional[List[List[str]]] = None
+                                           ) -> FeatureActivationDataset:
+    """The activation dataset of model ``g`` from the sparse codes ``sc`` (``engine.sparse_codes.SparseCodes``)
+    of the fragments' tokens: row ``i`` of ``sc`` is token ``i % L`` of fragment ``i // L``.  The same
+    ``acts`` / ``maxes`` (fp16, on the CPU) that ``make_feature_activation_dataset`` builds from dense
+    codes, features ``0 .. max_features - 1`` when ``max_features`` is set."""
+    F, L = fragments.shape
+    if sc.n_rows != F * L:
+        raise ValueError(f"the codes have {sc.n_rows} rows, {F} fragments of {L} tokens need {F * L} "
+                         "(narrow_rows drops padding rows)")
+    sc.check()
+    n = min(max_features, sc.n) if max_features else sc.n
+    stored = int(sc.row_ptr[g, -1])
+    cols, vals = sc.col[g, :stored].long(), sc.val[g, :stored]
+    rows = sc.entry_rows(g)
+    if n < sc.n:
+        keep = cols < n
+        rows, cols, vals = rows[keep], cols[keep], vals[keep]
+    acts = torch.zeros(F * L, n, dtype=torch.float16)
+    acts[rows.cpu(), cols.cpu()] = vals.to("cpu", torch.float16)
+    acts = acts.view(F, L, n)
+    # (fp16 rounding is monotone: the max of the rounded values is the rounded max)
+    return FeatureActivationDataset(fragments.to(torch.int32).cpu(), acts, acts.max(dim=1).values, token_strs)
+
+
+@torch.no_grad()
+def ensemble_feature_activation_datasets(lm: HookedLM, trainer, layer: int, layer_loc: str, fragments: torch.Tensor,
+                                         max_features: int = 0, batch_size: int = 256, tokenizer=None,
+                                         budget: Optional[int] = None) -> List[FeatureActivationDataset]:
+    """One activation dataset per model of ``trainer`` (an ``EnsembleTrainer``) from ONE pass of the LM over
+    the fragments: the activations at (layer, layer_loc) are collected on the device, padded with zero rows
+    up to a multiple of the trainer's batch size, encoded by ``trainer.encode_sparse`` for all models at
+    once (``budget`` as there) and cut back to the fragments' rows -- no unstacking, no dense codes on the
+    device."""
+    dev = lm.device
+    name = tensor_name(layer, layer_loc)
+    F, L = fragments.shape
+    B = int(getattr(trainer.impl, "batch_size", trainer.batch_size))
+    n_pad = -(-F * L // B) * B
+    dtype = torch.bfloat16 if trainer.kind in ("fused-sae", "fused-topk") else torch.float32
+    rows = None
+    for i in range(0, F, batch_size):
+        toks = fragments[i:i + batch_size].to(dev)
+        _, cache = lm.run_with_cache(toks, names_filter=[name], return_type=None)
+        h = cache[name]
+        h = h.reshape(h.shape[0] * L, -1)
+        if rows is None:
+            rows = torch.zeros(n_pad, h.shape[-1], dtype=dtype, device=dev)
+        rows[i * L: i * L + h.shape[0]] = h.to(dtype)
+    sc = trainer.encode_sparse(rows, budget=budget).narrow_rows(0, F * L)
+    strs = None
+    if tokenizer is not None and hasattr(tokenizer, "convert_ids_to_tokens"):
+        strs = [tokenizer.convert_ids_to_tokens(r.tolist()) for r in fragments]
+    return [feature_activation_dataset_from_sparse(sc, g, fragments, max_features, strs)
+            for g in range(sc.n_models)]
+
+
 def get_dataset(learned_dict, lm: HookedLM, layer: int, layer_loc: str, n_feats: int, save_loc: str,
                 fragments: Callable[[], torch.Tensor], force_refresh: bool = False, **kw) -> FeatureActivationDataset:
     """Cached ``make_feature_activation_dataset`` (reference get_df)."""

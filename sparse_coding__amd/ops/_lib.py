@@ -60,6 +60,9 @@ def signatures():
         "sc_col_topk": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p],
         "sc_rowmatch_reduce": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_int, c_int,
                                c_void_p, c_long, c_int, c_int, c_void_p, c_void_p],
+        "sc_code_row_counts": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+        "sc_code_compact": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long,
+                            c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
