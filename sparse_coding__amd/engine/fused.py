@@ -1018,6 +1018,31 @@ class FusedSAEEnsemble:
         return sc.SparseCodes(N, n, row_ptr, col, val)
 
     @torch.no_grad()
+    def interference(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None):
+        """Expected interference of every feature of every model on ``rows`` [N, d] (N a positive multiple
+        of the batch size): an ``engine.interference.Interference`` whose ``expected`` [G, n] is the
+        activity-weighted capacity ``c_a / sum_b cos^2(a, b) c_b`` averaged over the rows on which the
+        feature fires (``eval.metrics.calc_expected_interference``), and ``capacity`` the static capacity.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract (``budget=int`` never
+        synchronises, ``None`` synchronises once), then ONE ``active_capacity`` launch over the result
+        (``csrc/interference.hip``) against the unit-norm bf16 shadow that ``atom_matches`` reads: the
+        cosines are those of the bf16-rounded dictionaries.  With a ``budget`` that is too small the rows
+        whose entries were dropped are left out and counted in ``skipped`` (``check()`` raises).
+        ``state``: the result of an earlier call to continue -- integer sums: chunk by chunk gives the
+        bits of one call on the whole pool.  Masked ensembles: atoms at or past ``dict_size[g]`` take no
+        part.  Parameters, moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and
+        captured graphs are left as they are."""
+        from . import interference as ic
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"interference: {why}")
+        if state is not None:
+            ic.check_state(state, self.n_models, self.n)
+        return ic.interference_fused(self.encode_sparse(rows, budget=budget), self.dec_shadow, self.nactive, state)
+
+    @torch.no_grad()
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` holding, for
         every ordered pair (g, h), the ``m`` (1..8) nearest atoms of model h for each atom of model g (cosine

@@ -435,6 +435,20 @@ class FusedTopKEnsemble:
         return sc.sparse_codes_from_picks(picks(), self.k, self.n, cap)
 
     @torch.no_grad()
+    def interference(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None):
+        """Expected interference of every feature of every model on ``rows`` [N, d]: an
+        ``engine.interference.Interference`` with the SAE engine's contract -- ``encode_sparse(rows,
+        budget=budget)`` (this engine's: from the picks), then one ``active_capacity`` launch over the
+        result against the bf16 ``shadow`` of the unit-norm dictionaries; ``state`` continues an earlier
+        call with the bits of one call on the whole pool.  Parameters, moments, shadows, window counts,
+        the step counter and captured graphs are left as they are."""
+        from . import interference as ic
+
+        if state is not None:
+            ic.check_state(state, self.n_models, self.n)
+        return ic.interference_fused(self.encode_sparse(rows, budget=budget), self.shadow, None, state)
+
+    @torch.no_grad()
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` with the
         SAE engine's contract (``m`` in 1..8; for g == h the nearest *other* atoms; lowest index among

@@ -388,6 +388,42 @@ class EnsembleTrainer:
                      for i in range(0, rows.shape[0], self.batch_size))
             return sc.sparse_codes_reference(codes, cap)
 
+    # ------------------------------------------------------------------ expected interference
+    def interference(self, rows: torch.Tensor, **kw):
+        """Expected interference of every feature of every model on ``rows`` [N, d]: an
+        ``engine.interference.Interference`` (keywords ``budget`` as ``encode_sparse``, ``state`` to continue
+        an earlier call).
+
+        The fused SAE and top-k engines run their ``interference`` (the ``active_capacity`` kernel over
+        their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows
+        it is given).  The analytic and eager engines with an untied / tied SAE signature run
+        ``encode_sparse`` (the oracle on their fp32 torch codes) and the fp64 oracle against their fp32
+        unit-norm dictionaries.  Data-parallel trainers and every other kind (top-k under the eager engine
+        included) raise ``NotImplementedError``."""
+        from ..eval.metrics import capacity_per_feature_lowrank
+        from . import interference as ic
+
+        if self.dp is not None:
+            raise NotImplementedError("interference: data-parallel replicas (parallel='dp'/'zero1') hold the same "
+                                      "models on different rows; collect it on one rank's engine")
+        if self.kind in ("fused-sae", "fused-topk"):
+            return self.impl.interference(rows.to(self.device), **kw)
+        if self.kind not in ("analytic", "eager") or analytic._KINDS.get(self.sig) is None:
+            raise NotImplementedError(f"interference: no code path for the {self.kind} engine with "
+                                      f"{getattr(self.sig, '__name__', self.sig)}")
+        state = kw.pop("state", None)
+        codes = self.encode_sparse(rows, **kw)
+        with torch.no_grad():
+            dicts = [ld.get_learned_dict().detach().float() for ld in self.impl.to_learned_dicts(self.device)]
+        stacked = torch.zeros(len(dicts), codes.n, dicts[0].shape[1], device=dicts[0].device)
+        for g, D in enumerate(dicts):
+            stacked[g, :D.shape[0]] = D
+        live = [D.shape[0] for D in dicts]
+        ref = ic.active_capacity_reference(codes.to(stacked.device), stacked, live)
+        out =ic.Interference(codes.n_rows, ref.qsum, ref.count, ref.skipped,
+                              capacity_per_feature_lowrank(stacked, live))
+        return out if state is None else state.merge(out)
+
     # ------------------------------------------------------------------ nearest-atom matching
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models: an ``engine.atom_match.AtomMatches`` -- for every ordered pair

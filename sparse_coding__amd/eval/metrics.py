@@ -214,6 +214,56 @@ def capacity_per_feature(model: LearnedDict) -> torch.Tensor:
     return torch.diagonal(sq) / sq.sum(dim=-1)
 
 
+def capacity_per_feature_lowrank(D: torch.Tensor, live=None) -> torch.Tensor:
+    """``capacity_per_feature`` without the [n, n] matrix, in fp64: for the dictionary ``D`` [n, d] or a
+    stack [G, n, d], ``sum_j (d_i . d_j)^2 = d_i^T (D^T D) d_i``, so with ``M = D^T D`` [d, d] and
+    ``q = ((D M) * D).sum(-1)`` the capacity is ``(d_i . d_i)^2 / q`` -- n d^2 operations instead of n^2 d.
+    ``live``: the number of atoms that exist (an int, or one count per model of a stack): atoms at or
+    past it take no part and read 0, as does an all-zero atom.  Never synchronises."""
+    Dd = D.detach().double()
+    if live is not None:
+        n = Dd.shape[-2]
+        lv = torch.as_tensor(live, device=Dd.device).reshape(-1, 1) if Dd.dim() == 3 \
+            else torch.as_tensor(live, device=Dd.device).reshape(())
+        keep = torch.arange(n, device=Dd.device) < lv
+        Dd = Dd * keep.unsqueeze(-1)
+    M = Dd.transpose(-1, -2) @ Dd
+    q = ((Dd @ M) * Dd).sum(-1)
+    self2 = (Dd * Dd).sum(-1) ** 2
+    return torch.where(q > 0, self2 / q.clamp(min=torch.finfo(torch.float64).tiny), torch.zeros_like(q))
+
+
+def calc_expected_interference(dictionary: torch.Tensor, batch: torch.Tensor) -> torch.Tensor:
+    """Activity-weighted capacity of Scherlis et al. 2022 on dense tensors (reference big_sweep.py:44-58):
+    ``dictionary`` [n, d], ``batch`` [B, n] codes.  With the atoms normalised (norms clamped at 1e-8),
+    ``totals[b, i] = sum_j cos^2(i, j) batch[b, j]`` and ``capacities = batch / clamp(totals, 1e-8)``; the
+    result [n] is the per-feature sum of the capacities over the rows, divided by the number of rows on
+    which the feature is non-zero (clamped at 1)."""
+    normed = dictionary / torch.clamp(torch.linalg.vector_norm(dictionary, dim=-1), min=1e-8).unsqueeze(-1)
+    cos2 = (normed @ normed.T) ** 2
+    totals = batch @ cos2.T
+    capacities = batch / torch.clamp(totals, min=1e-8)
+    fired = torch.count_nonzero(batch, dim=0).to(capacities.dtype)
+    return capacities.sum(dim=0) / torch.clamp(fired, min=1.0)
+
+
+def expected_interference(sparse_codes, D: torch.Tensor, nactive=None):
+    """``calc_expected_interference`` for every model of an ensemble from its sparse codes: an
+    ``engine.interference.Interference`` of ``sparse_codes`` (``engine.sparse_codes.SparseCodes``) against
+    the dictionaries ``D`` [G, n, d]; ``.expected`` [G, n] is the metric, ``.capacity`` the static
+    capacity.  ``nactive``: live atoms per model of a masked ensemble.  bf16 dictionaries on the GPU run
+    the ``active_capacity`` kernel (a missing kernel library is an error); anything else runs the fp64
+    torch oracle."""
+    from ..engine import interference as ic
+
+    if D.is_cuda and D.dtype == torch.bfloat16:
+        return ic.interference_fused(sparse_codes, D.contiguous(), nactive)
+    ref = ic.active_capacity_reference(sparse_codes, D, nactive)
+    live = ic.live_counts(nactive, D.shape[0], D.shape[1], D.device)
+    return ic.Interference(sparse_codes.n_rows, ref.qsum, ref.count, ref.skipped,
+                           capacity_per_feature_lowrank(D, live))
+
+
 # ------------------------------------------------------------------ activity statistics
 def calc_feature_n_active(codes: torch.Tensor) -> torch.Tensor:
     return (codes != 0).sum(dim=0)

@@ -63,6 +63,9 @@ def signatures():
         "sc_code_row_counts": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
         "sc_code_compact": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long,
                             c_void_p],
+        "sc_row_norm2": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+        "sc_active_capacity": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_long, c_long, c_long, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
