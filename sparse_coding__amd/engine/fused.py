@@ -1043,6 +1043,56 @@ class FusedSAEEnsemble:
         return ic.interference_fused(self.encode_sparse(rows, budget=budget), self.dec_shadow, self.nactive, state)
 
     @torch.no_grad()
+    def recon_profile(self, rows: torch.Tensor, *, max_kept: int = 32, keep=None, budget: Optional[int] = None,
+                      state=None):
+        """Truncated and ablated reconstruction error of every model on ``rows`` [N, d] (N a positive
+        multiple of the batch size): an ``engine.sparse_recon.ReconProfile`` whose ``fvu_prefix`` [G, J + 1]
+        is the FVU when only the j largest codes of every row are kept (j = 0 .. ``max_kept`` <= 64; equal
+        codes go to the lower feature index), ``fvu_full`` the FVU from all codes and -- with ``keep``, a
+        bool [G, n] feature mask or its ``keep_words`` -- ``fvu_keep`` / ``fvu_rest`` the FVU from the kept
+        features' codes and from the others'.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, then per batch ``prepare()``, one
+        ``recon_curve`` and one ``recon_split`` launch on the batch's row window (``csrc/sparse_recon.hip``)
+        against the unit-norm bf16 shadow that ``interference`` reads, and the variance bookkeeping of
+        ``evaluate()``; the per-row values are summed in fp64.  With a ``budget`` that is too small the rows
+        whose entries were dropped are left out and counted in ``skipped`` (``check()`` raises).  ``state``:
+        the result of an earlier call to continue -- chunk by chunk gives the bits of one call on the whole
+        pool.  Tied models with a fixed affine centering are measured in the centred space, as
+        ``evaluate()``.  Parameters, moments, shadows, ``feature_counts``, ``rows_seen``, the step counter
+        and captured graphs are left as they are."""
+        from . import sparse_recon as sr
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"recon_profile: {why}")
+        J = sr.check_max_kept(max_kept)
+        if state is not None:
+            sr.check_state(state, self.n_models, J, keep is not None, self.d)
+        codes = self.encode_sparse(rows, budget=budget)
+        B = self.batch_size
+        pool = self._x_bf16(rows)
+        batches = (self.prepare(pool[i:i + B]) for i in range(0, rows.shape[0], B))
+        return sr.recon_profile_fused(codes, self.dec_shadow, batches, J, keep, self.nactive, state)
+
+    @torch.no_grad()
+    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
+        """FVU of every model on ``rows`` when only its ``n_top`` most active features are kept, and the FVU
+        of the rest (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble):
+        (fvu_top [G], fvu_rest [G]) in fp64 on the device.  The features are ordered by the sum of their
+        codes on ``rows`` descending, then feature index ascending -- from ``feature_stats(rows)``, or from
+        ``stats``, an earlier ``FeatureStats`` of the same rows, to save that pass; masked ensembles rank
+        only the features below ``dict_size[g]``.  The mask goes through ``recon_profile(rows, max_kept=0,
+        keep=mask, budget=budget)``."""
+        from . import sparse_recon as sr
+
+        if stats is None:
+            stats = self.feature_stats(rows)
+        mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top, self.nactive)
+        prof = self.recon_profile(rows, max_kept=0, keep=mask, budget=budget)
+        return prof.fvu_keep, prof.fvu_rest
+
+    @torch.no_grad()
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` holding, for
         every ordered pair (g, h), the ``m`` (1..8) nearest atoms of model h for each atom of model g (cosine

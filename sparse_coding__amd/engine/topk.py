@@ -449,6 +449,41 @@ class FusedTopKEnsemble:
         return ic.interference_fused(self.encode_sparse(rows, budget=budget), self.shadow, None, state)
 
     @torch.no_grad()
+    def recon_profile(self, rows: torch.Tensor, *, max_kept: int = 32, keep=None, budget: Optional[int] = None,
+                      state=None):
+        """Truncated and ablated reconstruction error of every model on ``rows`` [N, d]: an
+        ``engine.sparse_recon.ReconProfile`` with the SAE engine's contract -- ``encode_sparse(rows,
+        budget=budget)`` (this engine's: from the picks), then per batch one ``recon_curve`` and one
+        ``recon_split`` launch on the batch's row window against the bf16 ``shadow`` of the unit-norm
+        dictionaries, and the variance bookkeeping of ``evaluate()``; ``state`` continues an earlier call
+        with the bits of one call on the whole pool.  Parameters, moments, shadows, window counts, the step
+        counter and captured graphs are left as they are."""
+        from . import sparse_recon as sr
+
+        J = sr.check_max_kept(max_kept)
+        if state is not None:
+            sr.check_state(state, self.n_models, J, keep is not None, self.d)
+        codes = self.encode_sparse(rows, budget=budget)
+        B = self.batch_size
+        pool = self._x_bf16(rows)
+        batches = (pool[i:i + B] for i in range(0, rows.shape[0], B))
+        return sr.recon_profile_fused(codes, self.shadow, batches, J, keep, None, state)
+
+    @torch.no_grad()
+    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
+        """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` when only its ``n_top`` most
+        active features are kept, and the FVU of the rest, with the SAE engine's contract: features ordered
+        by the sum of their codes (``feature_stats(rows)``, or a passed ``stats``) descending, then feature
+        index ascending; the mask goes through ``recon_profile(rows, max_kept=0, keep=mask)``."""
+        from . import sparse_recon as sr
+
+        if stats is None:
+            stats = self.feature_stats(rows)
+        mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top)
+        prof = self.recon_profile(rows, max_kept=0, keep=mask, budget=budget)
+        return prof.fvu_keep, prof.fvu_rest
+
+    @torch.no_grad()
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` with the
         SAE engine's contract (``m`` in 1..8; for g == h the nearest *other* atoms; lowest index among

@@ -424,6 +424,66 @@ class EnsembleTrainer:
                               capacity_per_feature_lowrank(stacked, live))
         return out if state is None else state.merge(out)
 
+    # ------------------------------------------------------------------ truncated / ablated reconstruction
+    def _recon_route(self, what: str):
+        """True for the fused engines, False for the torch route; raises for everything else."""
+        if self.dp is not None:
+            raise NotImplementedError(f"{what}: data-parallel replicas (parallel='dp'/'zero1') hold the same "
+                                      "models on different rows; collect it on one rank's engine")
+        if self.kind in ("fused-sae", "fused-topk"):
+            return True
+        if self.kind not in ("analytic", "eager") or analytic._KINDS.get(self.sig) is None:
+            raise NotImplementedError(f"{what}: no code path for the {self.kind} engine with "
+                                      f"{getattr(self.sig, '__name__', self.sig)}")
+        return False
+
+    def recon_profile(self, rows: torch.Tensor, **kw):
+        """Truncated and ablated reconstruction error of every model on ``rows`` [N, d]: an
+        ``engine.sparse_recon.ReconProfile`` (keywords ``max_kept``, ``keep``, ``budget`` as
+        ``encode_sparse``, ``state`` to continue an earlier call).
+
+        The fused SAE and top-k engines run their ``recon_profile`` (the ``recon_curve`` / ``recon_split``
+        kernels over their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models
+        on the rows it is given).  The analytic and eager engines with an untied / tied SAE signature run
+        ``encode_sparse`` (the oracle on their fp32 torch codes) and the fp64 oracle against their fp32
+        unit-norm dictionaries and the rows each model sees (``LearnedDict.center``).  Data-parallel
+        trainers and every other kind (top-k under the eager engine included) raise
+        ``NotImplementedError``."""
+        from . import sparse_recon as sr
+
+        if self._recon_route("recon_profile"):
+            return self.impl.recon_profile(rows.to(self.device), **kw)
+        state, keep, max_kept = kw.pop("state", None), kw.pop("keep", None), kw.pop("max_kept", 32)
+        codes = self.encode_sparse(rows, **kw)
+        with torch.no_grad():
+            lds = self.impl.to_learned_dicts(self.device)
+            dicts = [ld.get_learned_dict().detach().float() for ld in lds]
+            x = torch.stack([ld.center(rows.to(dicts[0].device, torch.float32)) for ld in lds])
+        stacked = torch.zeros(len(dicts), codes.n, dicts[0].shape[1], device=dicts[0].device)
+        for g, D in enumerate(dicts):
+            stacked[g, :D.shape[0]] = D
+        live = [D.shape[0] for D in dicts]
+        return sr.recon_profile_reference(codes.to(stacked.device), stacked, x, max_kept, keep, live, state)
+
+    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, **kw):
+        """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` [N, d] when only its ``n_top`` most
+        active features are kept, and the FVU of the rest
+        (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble; keywords
+        ``budget``, ``stats``).  Features are ordered by the sum of their codes descending, then feature
+        index ascending.  Routed as ``recon_profile``."""
+        from . import sparse_recon as sr
+
+        if self._recon_route("fvu_top_activating"):
+            return self.impl.fvu_top_activating(rows.to(self.device), n_top, **kw)
+        stats = kw.pop("stats", None)
+        if stats is None:
+            stats = self.feature_stats(rows)
+        sums = stats.sums[:, 0]
+        with torch.no_grad():
+            live = torch.tensor([ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)])
+        prof = self.recon_profile(rows, max_kept=0, keep=sr.top_features(sums, n_top, live), **kw)
+        return prof.fvu_keep, prof.fvu_rest
+
     # ------------------------------------------------------------------ nearest-atom matching
     def atom_matches(self, m: int = 1):
         """Nearest atoms across the models: an ``engine.atom_match.AtomMatches`` -- for every ordered pair

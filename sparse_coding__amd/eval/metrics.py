@@ -264,6 +264,36 @@ def expected_interference(sparse_codes, D: torch.Tensor, nactive=None):
                            capacity_per_feature_lowrank(D, live))
 
 
+def truncated_fvu(sparse_codes, D: torch.Tensor, x: torch.Tensor, max_kept: int = 32, keep=None, nactive=None):
+    """FVU of every model of an ensemble when only the j largest codes of every row are kept, j = 0 ..
+    ``max_kept``, from its sparse codes: an ``engine.sparse_recon.ReconProfile`` of ``sparse_codes``
+    (``engine.sparse_codes.SparseCodes``) against the unit-norm dictionaries ``D`` [G, n, d] and the rows
+    ``x`` the decoder sees ([N, d] shared or [G, N, d]); ``.fvu_prefix`` [G, J + 1] is the curve,
+    ``.fvu_full`` the FVU from all codes and, with ``keep`` (bool [G, n] or ``keep_words``), ``.fvu_keep`` /
+    ``.fvu_rest`` the FVU from the kept features and from the others.  ``nactive``: live atoms per model of a
+    masked ensemble.  bf16 dictionaries and rows on the GPU run the ``recon_curve`` / ``recon_split``
+    kernels (a missing kernel library is an error); anything else runs the fp64 torch oracle."""
+    from ..engine import sparse_recon as sr
+
+    if D.is_cuda and D.dtype == torch.bfloat16 and x.dtype == torch.bfloat16:
+        return sr.recon_profile_fused(sparse_codes, D.contiguous(), [x.to(D.device).contiguous()], max_kept, keep,
+                                      nactive)
+    return sr.recon_profile_reference(sparse_codes, D, x, max_kept, keep, nactive)
+
+
+def ensemble_fvu_top_activating(engine_or_trainer, activations: torch.Tensor, n_top: int = 2):
+    """``fraction_variance_unexplained_top_activating`` for every model of an ensemble: ``engine_or_trainer``
+    is a fused engine or an ``EnsembleTrainer`` (anything with ``fvu_top_activating`` and ``batch_size``).
+    The activations are trimmed to a multiple of the batch size.  Returns (rows used, fvu_top [G],
+    fvu_rest [G])."""
+    B = int(getattr(getattr(engine_or_trainer, "impl", None), "batch_size", engine_or_trainer.batch_size))
+    N = activations.shape[0] - activations.shape[0] % B
+    if N == 0:
+        raise ValueError(f"need at least {B} rows")
+    top, rest = engine_or_trainer.fvu_top_activating(activations[:N], n_top)
+    return N, top, rest
+
+
 # ------------------------------------------------------------------ activity statistics
 def calc_feature_n_active(codes: torch.Tensor) -> torch.Tensor:
     return (codes != 0).sum(dim=0)

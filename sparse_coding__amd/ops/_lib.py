@@ -66,6 +66,10 @@ def signatures():
         "sc_row_norm2": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
         "sc_active_capacity": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_long, c_long, c_long, c_void_p],
+        "sc_recon_curve": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_int, c_long, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_void_p],
+        "sc_recon_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_int, c_long, c_int, c_int, c_long, c_long, c_long, c_long, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
