@@ -1076,6 +1076,30 @@ class FusedSAEEnsemble:
         return sr.recon_profile_fused(codes, self.dec_shadow, batches, J, keep, self.nactive, state)
 
     @torch.no_grad()
+    def feature_examples(self, rows: torch.Tensor, fragment_len: int = 64, n_top: int = 20, n_random: int = 20,
+                         seed: int = 0, budget: Optional[int] = None):
+        """Feature-major codes and example fragments of every feature of every model on ``rows`` [N, d] (N a
+        positive multiple of the batch size and of ``fragment_len``; row i is token ``i % fragment_len`` of
+        fragment ``i // fragment_len``): an ``engine.feature_codes.FeatureCodes`` and its ``FragmentExamples``
+        -- per feature the ``n_top`` fragments with the largest maximum code (ties to the lower fragment) and
+        a hash sample of ``n_random`` fragments on which it fires (both in 0..32).
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, then the transposition and one walk
+        over every feature's list (``csrc/feature_codes.hip``); no dense codes.  With a ``budget`` that is too
+        small the rows whose entries were dropped are left out whole and counted in ``skipped`` (``check()``
+        raises).  Masked ensembles: features at or past ``dict_size[g]`` have empty lists.  Parameters,
+        moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as
+        they are."""
+        from . import feature_codes as fc
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"feature_examples: {why}")
+        fc.check_fragments(rows.shape[0], fragment_len)
+        return fc.feature_examples(self.encode_sparse(rows, budget=budget), self.nactive, fragment_len, n_top,
+                                   n_random, seed)
+
+    @torch.no_grad()
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
         """FVU of every model on ``rows`` when only its ``n_top`` most active features are kept, and the FVU
         of the rest (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble):

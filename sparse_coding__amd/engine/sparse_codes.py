@@ -101,6 +101,17 @@ class SparseCodes:
         hit = self.col[g, :stored] == f
         return self.entry_rows(g)[hit], self.val[g, :stored][hit]
 
+    def by_feature(self, nactive=None, **kw):
+        """The feature-major transposition of these codes, an ``engine.feature_codes.FeatureCodes``: per model
+        and feature the rows on which it fires, ascending, with their codes -- ``feature_entries`` for every
+        feature at once, each a slice.  Rows whose entries are not all stored (overflowed buffers) or not valid
+        (a column outside [0, n), or [0, ``nactive[g]``) for masked ensembles) are left out whole and counted in
+        ``skipped``.  The kernels of ``csrc/feature_codes.hip`` when the tensors are on a GPU (never
+        synchronises; ``kw``: their launch geometry), the torch oracle elsewhere."""
+        from . import feature_codes as fc
+
+        return fc.by_feature(self, nactive, **kw)
+
     def to_torch_csr(self, g: int) -> torch.Tensor:
         """Model ``g`` as a ``torch.sparse_csr_tensor`` [n_rows, n] (fp32 values, int64 indices)."""
         self.check()

@@ -470,6 +470,20 @@ class FusedTopKEnsemble:
         return sr.recon_profile_fused(codes, self.shadow, batches, J, keep, None, state)
 
     @torch.no_grad()
+    def feature_examples(self, rows: torch.Tensor, fragment_len: int = 64, n_top: int = 20, n_random: int = 20,
+                         seed: int = 0, budget: Optional[int] = None):
+        """Feature-major codes and example fragments of every feature of every model on ``rows`` [N, d]: an
+        ``engine.feature_codes.FeatureCodes`` and its ``FragmentExamples`` with the SAE engine's contract --
+        ``encode_sparse(rows, budget=budget)`` (this engine's: from the picks), the transposition and one walk
+        over every feature's list (``csrc/feature_codes.hip``).  Parameters, moments, shadows, window counts,
+        the step counter and captured graphs are left as they are."""
+        from . import feature_codes as fc
+
+        fc.check_fragments(rows.shape[0], fragment_len)
+        return fc.feature_examples(self.encode_sparse(rows, budget=budget), None, fragment_len, n_top, n_random,
+                                   seed)
+
+    @torch.no_grad()
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` when only its ``n_top`` most
         active features are kept, and the FVU of the rest, with the SAE engine's contract: features ordered

@@ -465,6 +465,30 @@ class EnsembleTrainer:
         live = [D.shape[0] for D in dicts]
         return sr.recon_profile_reference(codes.to(stacked.device), stacked, x, max_kept, keep, live, state)
 
+    # ------------------------------------------------------------------ feature-major codes and example fragments
+    def feature_examples(self, rows: torch.Tensor, **kw):
+        """Feature-major codes and example fragments of every feature of every model on ``rows`` [N, d]: an
+        ``engine.feature_codes.FeatureCodes`` and its ``FragmentExamples`` (keywords ``fragment_len``, ``n_top``,
+        ``n_random``, ``seed``, ``budget`` as ``encode_sparse``).
+
+        The fused SAE and top-k engines run their ``feature_examples`` (the kernels of
+        ``csrc/feature_codes.hip`` over their own ``encode_sparse``; under ensemble sharding each rank gets this
+        rank's models on the rows it is given).  The analytic and eager engines with an untied / tied SAE
+        signature run ``encode_sparse`` (the oracle on their fp32 torch codes) and the torch oracles.
+        Data-parallel trainers and every other kind (top-k under the eager engine included) raise
+        ``NotImplementedError``."""
+        from . import feature_codes as fc
+
+        if self._recon_route("feature_examples"):
+            return self.impl.feature_examples(rows.to(self.device), **kw)
+        budget = kw.pop("budget", None)
+        fc.check_fragments(rows.shape[0], kw.get("fragment_len", 64))
+        codes = self.encode_sparse(rows, budget=budget)
+        with torch.no_grad():
+            live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
+        feats = fc.feature_codes_reference(codes, live)
+        return feats, fc.fragment_examples_reference(feats, **kw)
+
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, **kw):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` [N, d] when only its ``n_top`` most
         active features are kept, and the FVU of the rest

@@ -64,6 +64,10 @@ class FeatureActivationDataset:
             return None
         return active[torch.randperm(active.numel(), generator=generator)[:k]]
 
+    def fragment_acts(self, feat: int, idx: int) -> torch.Tensor:
+        """The [L] activations of ``feat`` on fragment ``idx``."""
+        return self.acts[idx, :, feat]
+
     def to_dataframe(self):
         """Reference column layout (``fragment_token_ids``, ``feature_i_max``,
         ``feature_i_activation_j``)."""
@@ -180,6 +184,133 @@ def ensemble_feature_activation_datasets(lm: HookedLM, trainer, layer: int, laye
         strs = [tokenizer.convert_ids_to_tokens(r.tolist()) for r in fragments]
     return [feature_activation_dataset_from_sparse(sc, g, fragments, max_features, strs)
             for g in range(sc.n_models)]
+
+
+@dataclass
+class FeatureExampleSet:
+    """What auto-interpretation reads of one model, without the dense ``acts``: per feature the number of
+    fragments on which it fires, its top fragments (largest maximum first, ties to the lower fragment) and a
+    hash sample of its active fragments (``engine.feature_codes``), each with its [L] activation record.
+    ``autointerp.feature_record`` / ``interpret`` run on it as on a ``FeatureActivationDataset``."""
+
+    token_ids: torch.Tensor     # [F, L] int32
+    n_frags: torch.Tensor       # [n] int64
+    top_frag: torch.Tensor      # [n, K] int32, -1: empty slot
+    top_acts: torch.Tensor      # [n, K, L] fp16
+    rand_frag: torch.Tensor     # [n, K] int32, -1: empty slot
+    rand_acts: torch.Tensor     # [n, K, L] fp16
+    token_strs: Optional[List[List[str]]] = None
+
+    @property
+    def n_feats(self) -> int:
+        return self.n_frags.shape[0]
+
+    def __len__(self):
+        return self.token_ids.shape[0]
+
+    def save(self, path: str):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        torch.save({"token_ids": self.token_ids, "n_frags": self.n_frags, "top_frag": self.top_frag,
+                    "top_acts": self.top_acts, "rand_frag": self.rand_frag, "rand_acts": self.rand_acts,
+                    "token_strs": self.token_strs}, path)
+
+    @classmethod
+    def load(cls, path: str) -> "FeatureExampleSet":
+        d = torch.load(path, weights_only=True)
+        return cls(d["token_ids"], d["n_frags"], d["top_frag"], d["top_acts"], d["rand_frag"], d["rand_acts"],
+                   d.get("token_strs"))
+
+    def _first(self, table: torch.Tensor, feat: int, k: int, what: str) -> torch.Tensor:
+        if k > table.shape[1]:
+            raise ValueError(f"{k} {what} fragments asked for, {table.shape[1]} are stored per feature")
+        t = table[feat, :k]
+        return t[t >= 0].long()
+
+    def top_fragments(self, feat: int, k: int) -> torch.Tensor:
+        """Indices of the (at most) ``k`` active fragments with the largest max activation of ``feat``."""
+        return self._first(self.top_frag, feat, k, "top")
+
+    def random_active_fragments(self, feat: int, k: int, generator: Optional[torch.Generator] = None
+                                ) -> Optional[torch.Tensor]:
+        """``k`` fragments on which ``feat`` fires; None if fewer exist.  The sample is the stored hash sample's
+        first ``k`` (itself a sample of size k, fixed by the seed the set was built with): ``generator`` is
+        accepted for the dense dataset's signature and not used."""
+        if int(self.n_frags[feat]) < k:
+            return None
+        return self._first(self.rand_frag, feat, k, "random")
+
+    def fragment_acts(self, feat: int, idx: int) -> torch.Tensor:
+        """The [L] activations of ``feat`` on fragment ``idx``, one of its stored top or random fragments."""
+        for frag, acts in ((self.top_frag, self.top_acts), (self.rand_frag, self.rand_acts)):
+            hit = torch.nonzero(frag[feat] == int(idx)).flatten()
+            if hit.numel():
+                return acts[feat, int(hit[0])]
+        raise KeyError(f"fragment {idx} is not among the stored examples of feature {feat}")
+
+
+def feature_example_sets_from_codes(fc, ex, fragments: torch.Tensor, token_strs: Optional[List[List[str]]] = None,
+                                    feature_chunk: int = 256) -> List[FeatureExampleSet]:
+    """One ``FeatureExampleSet`` per model from feature-major codes ``fc`` (``engine.feature_codes.FeatureCodes``)
+    and their ``FragmentExamples`` ``ex``.  The records are gathered ``feature_chunk`` features at a time
+    (``FeatureCodes.fragment_acts``), so the fp32 staging stays at G * chunk * K * L values."""
+    F, L = fragments.shape
+    if fc.n_rows != F * L or ex.fragment_len != L:
+        raise ValueError(f"the codes have {fc.n_rows} rows in fragments of {ex.fragment_len}, {F} fragments of {L} "
+                         "tokens were given")
+    G, n = fc.n_models, fc.n
+    tables = {"top": ex.top_frag, "rand": ex.rand_frag}
+    acts = {k: torch.empty(G, n, t.shape[2], L, dtype=torch.float16) for k, t in tables.items()}
+    for f0 in range(0, n, feature_chunk):
+        f1 = min(n, f0 + feature_chunk)
+        for k, t in tables.items():
+            rec = fc.fragment_acts(t[:, f0:f1].contiguous(), slice(f0, f1), L)
+            acts[k][:, f0:f1] = rec.to("cpu", torch.float16)
+    ids = fragments.to(torch.int32).cpu()
+    n_frags, top, rnd = ex.n_frags.cpu(), ex.top_frag.cpu(), ex.rand_frag.cpu()
+    return [FeatureExampleSet(ids, n_frags[g], top[g], acts["top"][g], rnd[g], acts["rand"][g], token_strs)
+            for g in range(G)]
+
+
+@torch.no_grad()
+def ensemble_feature_example_sets(lm: HookedLM, trainer, layer: int, layer_loc: str, fragments: torch.Tensor,
+                                  n_examples: Optional[int] = None, seed: int = 0, budget: Optional[int] = None,
+                                  tokenizer=None, batch_size: int = 256) -> List[FeatureExampleSet]:
+    """One ``FeatureExampleSet`` per model of ``trainer`` (an ``EnsembleTrainer``) from ONE pass of the LM over
+    the fragments, with no dense ``[F * L, n]`` code tensor on any device: the activations at (layer,
+    layer_loc) are collected on the device and go through ``trainer.feature_examples`` (sparse codes for all
+    models at once, the feature-major transposition, ``n_examples`` -- default ``autointerp.TOTAL_EXAMPLES`` --
+    top and random fragments per feature).  When the fragments' rows are no multiple of the trainer's batch
+    size they are padded with zero rows for ``encode_sparse``, the codes are cut back to the fragments' rows
+    (``narrow_rows``) and transposed from there, so a padding row is never an example."""
+    from ..engine import feature_codes as fcm
+
+    if n_examples is None:
+        from .autointerp import TOTAL_EXAMPLES as n_examples
+    dev = lm.device
+    name = tensor_name(layer, layer_loc)
+    F, L = fragments.shape
+    B = int(getattr(trainer.impl, "batch_size", trainer.batch_size))
+    n_pad = -(-F * L // B) * B
+    dtype = torch.bfloat16 if trainer.kind in ("fused-sae", "fused-topk") else torch.float32
+    rows = None
+    for i in range(0, F, batch_size):
+        toks = fragments[i:i + batch_size].to(dev)
+        _, cache = lm.run_with_cache(toks, names_filter=[name], return_type=None)
+        h = cache[name]
+        h = h.reshape(h.shape[0] * L, -1)
+        if rows is None:
+            rows = torch.zeros(n_pad, h.shape[-1], dtype=dtype, device=dev)
+        rows[i * L: i * L + h.shape[0]] = h.to(dtype)
+    if n_pad == F * L:
+        fc, ex = trainer.feature_examples(rows, fragment_len=L, n_top=n_examples, n_random=n_examples, seed=seed,
+                                          budget=budget)
+    else:
+        sc = trainer.encode_sparse(rows, budget=budget).narrow_rows(0, F * L)
+        fc, ex = fcm.feature_examples(sc, getattr(trainer.impl, "nactive", None), L, n_examples, n_examples, seed)
+    strs = None
+    if tokenizer is not None and hasattr(tokenizer, "convert_ids_to_tokens"):
+        strs = [tokenizer.convert_ids_to_tokens(r.tolist()) for r in fragments]
+    return feature_example_sets_from_codes(fc, ex, fragments, strs)
 
 
 def get_dataset(learned_dict, lm: HookedLM, layer: int, layer_loc: str, n_feats: int, save_loc: str,

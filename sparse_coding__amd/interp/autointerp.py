@@ -158,7 +158,7 @@ def _records(ds: FeatureActivationDataset, feat: int, idx: torch.Tensor, detok) 
     out = []
     for i in idx.tolist():
         toks = ds.token_strs[i] if ds.token_strs is not None else [detok(t) for t in ds.token_ids[i].tolist()]
-        out.append(ActivationRecord(list(toks), ds.acts[i, :, feat].float().tolist()))
+        out.append(ActivationRecord(list(toks), ds.fragment_acts(feat, i).float().tolist()))
     return out
 
 

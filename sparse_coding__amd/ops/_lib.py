@@ -70,6 +70,16 @@ def signatures():
                            c_int, c_long, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_void_p],
         "sc_recon_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_int, c_long, c_int, c_int, c_long, c_long, c_long, c_long, c_void_p],
+        "sc_feature_count": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_long, c_long,
+                             c_int, c_int, c_int, c_int, c_void_p],
+        "sc_feature_scatter": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_int, c_long, c_int, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_void_p],
+        "sc_feature_order": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                             c_long, c_long, c_void_p],
+        "sc_fragment_examples": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_long, c_long, c_int, c_int, C.c_uint, c_void_p],
+        "sc_fragment_acts": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_int, c_int,
+                             c_int, c_int, c_long, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
