@@ -1100,6 +1100,31 @@ class FusedSAEEnsemble:
                                    n_random, seed)
 
     @torch.no_grad()
+    def coactivation(self, rows: torch.Tensor, *, m: int = 4, score: str = "pearson", min_both: int = 1,
+                     budget: Optional[int] = None):
+        """Co-activation partners across the models of the ensemble on ``rows`` [N, d] (N a positive multiple of
+        the batch size): an ``engine.coactivation.CoActivation`` holding, for every ordered pair (g, h), the
+        ``m`` (0..32) features of model h that fire with each feature of model g on at least ``min_both`` rows
+        and score best (``score``: "pearson", "cosine" or "jaccard" of their codes; for g == h the best *other*
+        features): what the atoms alone cannot tell -- feature splitting, or two close atoms that fire on
+        different rows.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, then the transposition, the list
+        moments and one walk per (feature, model) over the feature's list (``csrc/coactivation.hip``); no dense
+        codes and no [n, n] matrix.  With a ``budget`` that is too small the rows whose entries were dropped are
+        left out whole and counted in ``skipped_a`` / ``skipped_b`` (``check()`` raises).  Masked ensembles:
+        features at or past ``dict_size[g]`` have no partners and are nobody's.  There is no ``state=``: the m
+        best of a sum cannot be merged across chunks, so the pool is given whole.  Parameters, moments,
+        shadows, ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as they are."""
+        from . import coactivation as co
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"coactivation: {why}")
+        return co.coactivation(self.encode_sparse(rows, budget=budget), m=m, score=score, min_both=min_both,
+                               nactive_a=self.nactive)
+
+    @torch.no_grad()
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
         """FVU of every model on ``rows`` when only its ``n_top`` most active features are kept, and the FVU
         of the rest (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble):

@@ -112,6 +112,17 @@ class SparseCodes:
 
         return fc.by_feature(self, nactive, **kw)
 
+    def coactivation(self, other: Optional["SparseCodes"] = None, **kw):
+        """The best co-activation partners of every feature of every model among the features of every model of
+        ``other`` (default: these codes themselves), an ``engine.coactivation.CoActivation``: which features
+        fire on the same rows, and how correlated their codes are (keywords ``m``, ``score``, ``min_both``,
+        ``exclude_self``, ``nactive_a``, ``nactive_b`` of ``engine.coactivation.coactivation``).  Both sides
+        cover the same rows.  The kernels of ``csrc/coactivation.hip`` when the tensors are on a GPU (never
+        synchronises), the torch oracle elsewhere.  There is no ``state=``: a pool is given whole."""
+        from . import coactivation as co
+
+        return co.coactivation(self, other, **kw)
+
     def to_torch_csr(self, g: int) -> torch.Tensor:
         """Model ``g`` as a ``torch.sparse_csr_tensor`` [n_rows, n] (fp32 values, int64 indices)."""
         self.check()

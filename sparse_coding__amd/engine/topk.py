@@ -484,6 +484,19 @@ class FusedTopKEnsemble:
                                    seed)
 
     @torch.no_grad()
+    def coactivation(self, rows: torch.Tensor, *, m: int = 4, score: str = "pearson", min_both: int = 1,
+                     budget: Optional[int] = None):
+        """Co-activation partners across the models of the ensemble on ``rows`` [N, d]: an
+        ``engine.coactivation.CoActivation`` with the SAE engine's contract -- ``encode_sparse(rows,
+        budget=budget)`` (this engine's: from the picks), the transposition, the list moments and one walk per
+        (feature, model) over the feature's list (``csrc/coactivation.hip``).  There is no ``state=``: the pool
+        is given whole.  Parameters, moments, shadows, window counts, the step counter and captured graphs are
+        left as they are."""
+        from . import coactivation as co
+
+        return co.coactivation(self.encode_sparse(rows, budget=budget), m=m, score=score, min_both=min_both)
+
+    @torch.no_grad()
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` when only its ``n_top`` most
         active features are kept, and the FVU of the rest, with the SAE engine's contract: features ordered

@@ -489,6 +489,28 @@ class EnsembleTrainer:
         feats = fc.feature_codes_reference(codes, live)
         return feats, fc.fragment_examples_reference(feats, **kw)
 
+    # ------------------------------------------------------------------ co-activation partners
+    def coactivation(self, rows: torch.Tensor, **kw):
+        """Co-activation partners across the models on ``rows`` [N, d]: an ``engine.coactivation.CoActivation``
+        -- for every ordered pair (g, h) the features of model h that fire on the same rows as each feature of
+        model g and score best (keywords ``m``, ``score``, ``min_both``, ``budget`` as ``encode_sparse``).  There
+        is no ``state=``: the pool is given whole.
+
+        The fused SAE and top-k engines run their ``coactivation`` (the kernels of ``csrc/coactivation.hip`` over
+        their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows it is
+        given).  The analytic and eager engines with an untied / tied SAE signature run ``encode_sparse`` (the
+        oracle on their fp32 torch codes) and the torch oracle.  Data-parallel trainers and every other kind
+        (top-k under the eager engine included) raise ``NotImplementedError``."""
+        from . import coactivation as co
+
+        if self._recon_route("coactivation"):
+            return self.impl.coactivation(rows.to(self.device), **kw)
+        budget = kw.pop("budget", None)
+        codes = self.encode_sparse(rows, budget=budget)
+        with torch.no_grad():
+            live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
+        return co.coactivation_reference(codes, nactive_a=live, **kw)
+
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, **kw):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` [N, d] when only its ``n_top`` most
         active features are kept, and the FVU of the rest

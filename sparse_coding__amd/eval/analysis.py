@@ -91,6 +91,35 @@ def nearest_with_larger(learned_dicts: Sequence[Sequence[torch.Tensor]], thresho
     return av, above, full, matched
 
 
+def splitting_with_larger(learned_dicts: Sequence[Sequence[torch.Tensor]], sparse_codes: Sequence[Sequence[object]],
+                          m: int = 4, score: str = "pearson", min_both: int = 1):
+    """Feature splitting between each dictionary and the next larger one, shaped like ``nearest_with_larger``:
+    ``learned_dicts[l1][size]`` are the dictionaries and ``sparse_codes[l1][size]`` the single-model
+    ``SparseCodes`` of each on the SAME rows.  Returns (mean best activation score [L, S], mean share of a
+    feature's activation partners that are not its nearest atom [L, S], per-cell ``CoActivation`` [L][S-1],
+    per-cell nearest-atom (cosine, index) arrays [L][S-1]).  Per feature of the smaller dictionary, cell (i, j)
+    holds its ``m`` activation partners in the larger one (``eval.metrics.activation_matches``) next to its
+    nearest atom there: a feature that splits has several partners with a high score and only one of them
+    is its nearest atom."""
+    L, S = len(learned_dicts), len(learned_dicts[0])
+    av = np.zeros((L, S))
+    other = np.zeros((L, S))
+    partners = [[None] * (S - 1) for _ in range(L)]
+    nearest = [[None] * (S - 1) for _ in range(L)]
+    for i in range(L):
+        for j in range(S - 1):
+            co = M.activation_matches(sparse_codes[i][j], sparse_codes[i][j + 1], m=m, score=score, min_both=min_both)
+            sims, idx = nearest_max_cosine(learned_dicts[i][j], learned_dicts[i][j + 1])
+            part = co.partner[0, 0].cpu()
+            fires = (co.cnt_a[0] > 0).cpu()
+            have = part >= 0
+            av[i, j] = float(co.mean_best()[0, 0])
+            off = (have & (part != torch.as_tensor(idx).view(-1, 1))).sum(1).double() / have.sum(1).clamp(min=1)
+            other[i, j] = float(off[fires].mean()) if bool(fires.any()) else 0.0
+            partners[i][j], nearest[i][j] = co, (sims, idx)
+    return av, other, partners, nearest
+
+
 def effective_number_of_neurons(features: torch.Tensor) -> torch.Tensor:
     p = features.abs() / features.abs().sum(dim=1, keepdim=True)
     return 1.0 / p.pow(2).sum(dim=1)

@@ -136,6 +136,19 @@ def nearest_atoms(rows: torch.Tensor, against: torch.Tensor, m: int = 1, exclude
     return cos, idx
 
 
+def activation_matches(sc_small, sc_large, m: int = 4, score: str = "pearson", min_both: int = 1):
+    """Nearest features by ACTIVATION between two ensembles whose sparse codes ``sc_small`` / ``sc_large``
+    (``engine.sparse_codes.SparseCodes`` of the smaller and the larger dictionaries) cover the same rows: an
+    ``engine.coactivation.CoActivation`` [G_small, G_large, n_small, m] -- per feature of a smaller dictionary
+    the ``m`` features of each larger one that fire on the same rows and score best (``score``: "pearson",
+    "cosine" or "jaccard" of their codes).  ``nearest_atoms`` compares the atoms; two close atoms may fire on
+    different rows, and a feature that splits keeps modest cosines with partners that fire exactly where it
+    does.  The kernels of ``csrc/coactivation.hip`` on a GPU, the torch oracle elsewhere."""
+    from ..engine.coactivation import coactivation
+
+    return coactivation(sc_small, sc_large, m=m, score=score, min_both=min_both, exclude_self=False)
+
+
 def mutual_nearest(a: torch.Tensor, b: torch.Tensor, fused: bool | None = None
                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The pairs (i, j) with b_j the nearest atom of a_i and a_i the nearest atom of b_j: (ia, ib, cos),

@@ -80,6 +80,11 @@ def signatures():
                                  c_long, c_long, c_int, c_int, C.c_uint, c_void_p],
         "sc_fragment_acts": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_int, c_int,
                              c_int, c_int, c_long, c_void_p],
+        "sc_list_moments": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p],
+        "sc_coactivation_topm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_int, c_long, c_int, c_int, c_long, c_long, c_long, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
