@@ -1125,6 +1125,28 @@ class FusedSAEEnsemble:
                                nactive_a=self.nactive)
 
     @torch.no_grad()
+    def label_profile(self, rows: torch.Tensor, labels: torch.Tensor, *, budget: Optional[int] = None, **kw):
+        """Per feature of every model the labels that carry its activations on ``rows`` [N, d] (N a positive
+        multiple of the batch size): an ``engine.label_profile.LabelProfile``.  ``labels`` int32 / int64 [N]
+        gives every row a label -- its token id, its position, a concept flag; a negative one leaves the row out
+        -- and the profile holds per feature its ``m`` best labels by ``rank_by`` with their counts, fp64 sums
+        and maxima, and the totals that turn them into shares, precision and recall (keywords ``m``,
+        ``rank_by``, ``n_classes`` of ``engine.label_profile.label_profile``).
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, the kept rows gathered in label order
+        (``SparseCodes.take_rows``), the transposition and one walk per feature list
+        (``csrc/label_profile.hip``); no dense codes and no global sort of the entries.  The codes must be
+        complete: a ``budget`` that is too small raises ``SparseCodesOverflow``.  Masked ensembles: features at
+        or past ``dict_size[g]`` have empty profiles.  Parameters, moments, shadows, ``feature_counts``,
+        ``rows_seen``, the step counter and captured graphs are left as they are."""
+        from . import label_profile as lp
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"label_profile: {why}")
+        return lp.label_profile(self.encode_sparse(rows, budget=budget), labels, nactive=self.nactive, **kw)
+
+    @torch.no_grad()
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
         """FVU of every model on ``rows`` when only its ``n_top`` most active features are kept, and the FVU
         of the rest (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble):

@@ -150,6 +150,37 @@ class SparseCodes:
         return SparseCodes(hi - lo, self.n, (self.row_ptr[:, lo:hi + 1] - start.unsqueeze(1)).contiguous(),
                            col.contiguous(), val.contiguous())
 
+    def take_rows(self, index: torch.Tensor, **kw) -> "SparseCodes":
+        """Rows ``index`` (int64 [M], each in [0, n_rows), duplicates allowed) as a ``SparseCodes`` over M rows:
+        row ``i`` of the result is row ``index[i]`` of these codes, columns and values copied bit for bit, in
+        order.  The new ``row_ptr`` is a device cumsum of the gathered row lengths and ``cap`` is exactly the
+        largest model's new entry count.  Needs complete codes; the one synchronisation is that of ``check()``
+        (its host copy also carries the new counts and the index check).  The ``sc_csr_take_rows`` kernel of
+        ``csrc/label_profile.hip`` when the tensors are on a GPU (``kw``: its ``waves``), ``take_rows_reference``
+        elsewhere.  ``narrow_rows(lo, hi)`` equals ``take_rows(arange(lo, hi))``."""
+        index = _check_index(index, self.row_ptr.device)
+        if not self.col.is_cuda:
+            if kw:
+                raise TypeError(f"take_rows: {sorted(kw)} are keywords of the device route")
+            return take_rows_reference(self, index)
+        from ..ops import sparse_codes as sc_ops
+
+        out_ptr, cap = _taken_row_ptr(self, index)
+        col, val = sc_ops.take_rows(self.row_ptr.contiguous(), self.col, self.val, index, out_ptr, cap, **kw)
+        return SparseCodes(int(index.shape[0]), self.n, out_ptr, col, val)
+
+    def label_profile(self, labels: torch.Tensor, **kw):
+        """Per feature of every model the labels that carry its activations, an
+        ``engine.label_profile.LabelProfile``: ``labels`` int32 / int64 [n_rows] gives every row a label (a token
+        id, a position, a concept; negative: the row is left out), and the profile holds per feature its ``m``
+        best labels with their counts, fp64 sums and maxima, and the totals that turn them into shares,
+        precision and recall (keywords ``m``, ``rank_by``, ``n_classes``, ``nactive`` of
+        ``engine.label_profile.label_profile``).  The kernels of ``csrc/label_profile.hip`` when the tensors are
+        on a GPU, the torch oracle elsewhere."""
+        from . import label_profile as lp
+
+        return lp.label_profile(self, labels, **kw)
+
     @classmethod
     def cat(cls, parts: Sequence["SparseCodes"]) -> "SparseCodes":
         """The rows of ``parts`` one after the other (same models, same width).  Synchronises; needs
@@ -194,6 +225,47 @@ class SparseCodes:
 
     def to(self, device) -> "SparseCodes":
         return SparseCodes(self.n_rows, self.n, self.row_ptr.to(device), self.col.to(device), self.val.to(device))
+
+
+def _check_index(index, device) -> torch.Tensor:
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1:
+        raise ValueError("index must be an int64 tensor [M]")
+    return index.to(device).contiguous()
+
+
+def _taken_row_ptr(sc: SparseCodes, index: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """``(row_ptr int64 [G, M + 1], cap)`` of ``sc.take_rows(index)``: the cumsum of the gathered row lengths on
+    the device, and the largest model's new entry count.  One host copy carries the overflow flags of ``check()``,
+    the new counts and the index check."""
+    G, N, M, dev = sc.n_models, sc.n_rows, int(index.shape[0]), sc.row_ptr.device
+    if N == 0 and M:
+        raise IndexError("take_rows: codes without rows have no row to take")
+    safe = index.clamp(0, max(N - 1, 0))
+    bad = ((index < 0) | (index >= N)).any().to(torch.int64).view(1)
+    out_ptr = torch.zeros(G, M + 1, dtype=torch.int64, device=dev)
+    out_ptr[:, 1:] = torch.cumsum(sc.row_ptr[:, safe + 1] - sc.row_ptr[:, safe], 1)
+    host = torch.cat([sc.row_ptr[:, -1], out_ptr[:, -1], bad]).cpu()   # the one synchronisation
+    if bool((host[:G] > sc.cap).any()):
+        sc.check()   # raises SparseCodesOverflow
+    if int(host[-1]):
+        raise IndexError(f"take_rows: index values must lie in [0, {N})")
+    return out_ptr, (int(host[G:2 * G].max()) if G else 0)
+
+
+def take_rows_reference(sc: SparseCodes, index: torch.Tensor) -> SparseCodes:
+    """Torch oracle of ``SparseCodes.take_rows`` (any device; this is what runs off the GPU)."""
+    index = _check_index(index, sc.row_ptr.device)
+    out_ptr, cap = _taken_row_ptr(sc, index)
+    G, dev = sc.n_models, sc.row_ptr.device
+    col = torch.zeros(G, cap, dtype=torch.int32, device=dev)
+    val = torch.zeros(G, cap, dtype=torch.float32, device=dev)
+    for g in range(G):
+        ln = out_ptr[g, 1:] - out_ptr[g, :-1]
+        k = int(out_ptr[g, -1])
+        src = torch.repeat_interleave(sc.row_ptr[g, index] - out_ptr[g, :-1], ln) + torch.arange(k, device=dev)
+        col[g, :k] = sc.col[g][src]
+        val[g, :k] = sc.val[g][src]
+    return SparseCodes(int(index.shape[0]), sc.n, out_ptr, col, val)
 
 
 def check_budget(budget, n_rows: int, n: int) -> Optional[int]:

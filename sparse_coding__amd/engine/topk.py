@@ -497,6 +497,18 @@ class FusedTopKEnsemble:
         return co.coactivation(self.encode_sparse(rows, budget=budget), m=m, score=score, min_both=min_both)
 
     @torch.no_grad()
+    def label_profile(self, rows: torch.Tensor, labels: torch.Tensor, *, budget: Optional[int] = None, **kw):
+        """Per feature of every model the labels that carry its activations on ``rows`` [N, d]: an
+        ``engine.label_profile.LabelProfile`` with the SAE engine's contract -- ``encode_sparse(rows,
+        budget=budget)`` (this engine's: from the picks), the kept rows gathered in label order, the
+        transposition and one walk per feature list (``csrc/label_profile.hip``; keywords ``m``, ``rank_by``,
+        ``n_classes``).  Parameters, moments, shadows, window counts, the step counter and captured graphs are
+        left as they are."""
+        from . import label_profile as lp
+
+        return lp.label_profile(self.encode_sparse(rows, budget=budget), labels, **kw)
+
+    @torch.no_grad()
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` when only its ``n_top`` most
         active features are kept, and the FVU of the rest, with the SAE engine's contract: features ordered

@@ -511,6 +511,27 @@ class EnsembleTrainer:
             live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
         return co.coactivation_reference(codes, nactive_a=live, **kw)
 
+    # ------------------------------------------------------------------ label profiles
+    def label_profile(self, rows: torch.Tensor, labels: torch.Tensor, **kw):
+        """Per feature of every model the labels that carry its activations on ``rows`` [N, d]: an
+        ``engine.label_profile.LabelProfile`` (``labels`` int32 / int64 [N], negative: the row is left out;
+        keywords ``m``, ``rank_by``, ``n_classes``, ``budget`` as ``encode_sparse``).
+
+        The fused SAE and top-k engines run their ``label_profile`` (the kernels of ``csrc/label_profile.hip``
+        over their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows
+        it is given).  The analytic and eager engines with an untied / tied SAE signature run ``encode_sparse``
+        (the oracle on their fp32 torch codes) and the torch oracle.  Data-parallel trainers and every other
+        kind (top-k under the eager engine included) raise ``NotImplementedError``."""
+        from . import label_profile as lp
+
+        if self._recon_route("label_profile"):
+            return self.impl.label_profile(rows.to(self.device), labels.to(self.device), **kw)
+        budget = kw.pop("budget", None)
+        codes = self.encode_sparse(rows, budget=budget)
+        with torch.no_grad():
+            live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
+        return lp.label_profile_reference(codes, labels, nactive=live, **kw)
+
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, **kw):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` [N, d] when only its ``n_top`` most
         active features are kept, and the FVU of the rest

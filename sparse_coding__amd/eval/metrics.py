@@ -149,6 +149,24 @@ def activation_matches(sc_small, sc_large, m: int = 4, score: str = "pearson", m
     return coactivation(sc_small, sc_large, m=m, score=score, min_both=min_both, exclude_self=False)
 
 
+def label_selectivity(sparse_codes, labels: torch.Tensor, n_classes: int, m: int = 1, nactive=None):
+    """Every feature as a detector of its best label: ``(label int32, precision, recall, f1)``, [G, n] each (fp64
+    scores), from the sparse codes of a pool (``engine.sparse_codes.SparseCodes``) and one label per row
+    (``labels`` int32 / int64 [n_rows] in [0, ``n_classes``); negative: the row is left out).  Precision is the
+    part of the feature's rows that carry the label, recall the part of the label's rows on which the feature
+    fires.  The best label is, among the feature's ``m`` most frequent labels, the one with the largest F1 (the
+    more frequent one among equals); with ``m`` = 1 it is the most frequent label.  A feature that never fires
+    reads ``(-1, 0, 0, 0)``.  From ``engine.label_profile.label_profile``: the kernels of
+    ``csrc/label_profile.hip`` on a GPU, the torch oracle elsewhere."""
+    from ..engine.label_profile import label_profile
+
+    prof = label_profile(sparse_codes, labels, m=m, rank_by="count", n_classes=n_classes, nactive=nactive)
+    p, r, f = prof.precision(), prof.recall(), prof.f1()
+    best = f.argmax(-1, keepdim=True)
+    pick = lambda t: t.gather(-1, best).squeeze(-1)
+    return pick(prof.top_label), pick(p), pick(r), pick(f)
+
+
 def mutual_nearest(a: torch.Tensor, b: torch.Tensor, fused: bool | None = None
                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The pairs (i, j) with b_j the nearest atom of a_i and a_i the nearest atom of b_j: (ia, ib, cos),

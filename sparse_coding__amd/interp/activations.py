@@ -313,6 +313,51 @@ def ensemble_feature_example_sets(lm: HookedLM, trainer, layer: int, layer_loc: 
     return feature_example_sets_from_codes(fc, ex, fragments, strs)
 
 
+def token_labels(fragments: torch.Tensor, context: str = "self", ignore: Sequence[int] = ()) -> torch.Tensor:
+    """One label per token of ``fragments`` [F, L], int64 [F * L] in row order: the token's own id (``context``
+    "self") or the id of the token before it ("prev"; the first token of a fragment has none and reads -1).
+    Token ids in ``ignore`` read -1: a negative label leaves the row out of a label profile."""
+    if context not in ("self", "prev"):
+        raise ValueError(f"context must be 'self' or 'prev', got {context!r}")
+    ids = fragments.to(torch.int64)
+    if context == "prev":
+        ids = torch.cat([torch.full_like(ids[:, :1], -1), ids[:, :-1]], dim=1)
+    for t in ignore:
+        ids = torch.where(ids == int(t), torch.full_like(ids, -1), ids)
+    return ids.reshape(-1)
+
+
+@torch.no_grad()
+def ensemble_token_profiles(lm: HookedLM, trainer, layer: int, layer_loc: str, fragments: torch.Tensor, m: int = 8,
+                            context: str = "self", ignore: Sequence[int] = (), rank_by: str = "sum",
+                            n_classes: Optional[int] = None, budget: Optional[int] = None, batch_size: int = 256):
+    """The token profile of every feature of every model of ``trainer`` (an ``EnsembleTrainer``): an
+    ``engine.label_profile.LabelProfile`` whose labels are token ids -- per feature the ``m`` tokens that carry
+    most of its activation over ALL fragments, where ``TokenStatsExplainer`` guesses them from a handful of
+    example fragments.  ONE pass of the LM over the fragments and ONE ``encode_sparse`` for all models: the
+    activations at (layer, layer_loc) are collected on the device, padded with zero rows up to a multiple of the
+    trainer's batch size (their label is -1, so a padding row is in no profile) and go through
+    ``trainer.label_profile`` with the labels of ``token_labels(fragments, context, ignore)``."""
+    dev = lm.device
+    name = tensor_name(layer, layer_loc)
+    F, L = fragments.shape
+    B = int(getattr(trainer.impl, "batch_size", trainer.batch_size))
+    n_pad = -(-F * L // B) * B
+    dtype = torch.bfloat16 if trainer.kind in ("fused-sae", "fused-topk") else torch.float32
+    rows = None
+    for i in range(0, F, batch_size):
+        toks = fragments[i:i + batch_size].to(dev)
+        _, cache = lm.run_with_cache(toks, names_filter=[name], return_type=None)
+        h = cache[name]
+        h = h.reshape(h.shape[0] * L, -1)
+        if rows is None:
+            rows = torch.zeros(n_pad, h.shape[-1], dtype=dtype, device=dev)
+        rows[i * L: i * L + h.shape[0]] = h.to(dtype)
+    labels = torch.full((n_pad,), -1, dtype=torch.int64)
+    labels[:F * L] = token_labels(fragments.cpu(), context, ignore)
+    return trainer.label_profile(rows, labels, m=m, rank_by=rank_by, n_classes=n_classes, budget=budget)
+
+
 def get_dataset(learned_dict, lm: HookedLM, layer: int, layer_loc: str, n_feats: int, save_loc: str,
                 fragments: Callable[[], torch.Tensor], force_refresh: bool = False, **kw) -> FeatureActivationDataset:
     """Cached ``make_feature_activation_dataset`` (reference get_df)."""

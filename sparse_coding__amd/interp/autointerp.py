@@ -94,6 +94,31 @@ class TokenListSimulator:
         return [1.0 if t in listed else 0.0 for t in tokens]
 
 
+class TokenProfileExplainer:
+    """Explanation = the ``k`` tokens that carry most of a feature's activation over the WHOLE pool, read from a
+    token profile (an ``engine.label_profile.LabelProfile`` whose labels are token ids,
+    ``activations.ensemble_token_profiles``) of model ``g`` -- where ``TokenStatsExplainer`` guesses them from
+    the handful of records it is shown.  ``for_feature(f)`` is the ``Explainer`` of feature ``f``; it ignores the
+    records.  ``detok`` maps a token id to the string the records carry.  Same ``"tokens: a | b"`` format, so
+    ``TokenListSimulator`` reads it."""
+
+    def __init__(self, profile, g: int, detok=str, k: int = 5, feature: Optional[int] = None):
+        if not 0 <= g < profile.n_models:
+            raise IndexError(f"model {g} outside [0, {profile.n_models})")
+        if feature is not None and not 0 <= feature < profile.n:
+            raise IndexError(f"feature {feature} outside [0, {profile.n})")
+        self.profile, self.g, self.detok, self.k, self.feature = profile, g, detok, k, feature
+
+    def for_feature(self, feature: int) -> "TokenProfileExplainer":
+        return TokenProfileExplainer(self.profile, self.g, self.detok, self.k, feature)
+
+    def explain(self, records=None, max_activation: float = 0.0):
+        if self.feature is None:
+            raise ValueError("TokenProfileExplainer.explain needs a feature: use for_feature(f)")
+        labels = self.profile.top_label[self.g, self.feature, :self.k].tolist()
+        return "tokens: " + " | ".join(self.detok(t) for t in labels if t >= 0)
+
+
 # ----------------------------------------------------------------------------- LLM endpoint
 class _Endpoint:
     def __init__(self, model: str, endpoint: Optional[str] = None, api_key: Optional[str] = None, timeout: float = 60):

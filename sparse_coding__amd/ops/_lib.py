@@ -85,6 +85,11 @@ def signatures():
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int, c_long, c_int, c_int, c_long, c_long, c_long, c_int, c_int,
                                  c_int, c_int, c_int, c_int, c_void_p],
+        "sc_csr_take_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long,
+                             c_long, c_long, c_long, c_long, c_int, c_void_p],
+        "sc_label_profile": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_int, c_int,
+                             c_int, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
