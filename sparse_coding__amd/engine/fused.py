@@ -1147,19 +1147,58 @@ class FusedSAEEnsemble:
         return lp.label_profile(self.encode_sparse(rows, budget=budget), labels, nactive=self.nactive, **kw)
 
     @torch.no_grad()
-    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
+    def attribution(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None,
+                    return_proj: bool = False):
+        """What every feature of every model does for the reconstruction of ``rows`` [N, d] (N a positive
+        multiple of the batch size): an ``engine.attribution.Attribution`` whose ``delta_sse`` [G, n] is the
+        exact rise of the summed squared error when the feature alone is removed, ``rescale`` the least-squares
+        factor on its codes (the shrinkage diagnostic of L1-trained SAEs), ``harmful_fraction`` how often its
+        firing makes its row worse, and ``top_mask(k)`` a keep mask for ``recon_profile``.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, then per batch ``prepare()`` and one
+        ``residual_proj`` launch on the batch's row window against the unit-norm bf16 shadow that
+        ``recon_profile`` reads, then ``by_feature`` and one ``attr_list_sums`` launch
+        (``csrc/attribution.hip``), and the variance bookkeeping of ``evaluate()``.  With a ``budget`` that is
+        too small the rows whose entries were dropped are left out and counted in ``skipped`` (``check()``
+        raises).  ``state``: the result of an earlier call to merge with (``Attribution.merge``).
+        ``return_proj``: keep the per-entry projections, aligned with the codes' ``col`` / ``val``.  Tied models
+        with a fixed affine centering are measured in the centred space.  Parameters, moments, shadows,
+        ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as they are."""
+        from . import attribution as at
+
+        why = self._stats_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"attribution: {why}")
+        if state is not None:
+            at.check_state(state, self.n_models, self.n, self.d)
+        codes = self.encode_sparse(rows, budget=budget)
+        B = self.batch_size
+        pool = self._x_bf16(rows)
+        batches = (self.prepare(pool[i:i + B]) for i in range(0, rows.shape[0], B))
+        return at.attribution_fused(codes, self.dec_shadow, batches, self.nactive, None, state,
+                                    return_proj=return_proj)
+
+    @torch.no_grad()
+    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None,
+                           rank_by: str = "sum"):
         """FVU of every model on ``rows`` when only its ``n_top`` most active features are kept, and the FVU
         of the rest (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble):
         (fvu_top [G], fvu_rest [G]) in fp64 on the device.  The features are ordered by the sum of their
         codes on ``rows`` descending, then feature index ascending -- from ``feature_stats(rows)``, or from
         ``stats``, an earlier ``FeatureStats`` of the same rows, to save that pass; masked ensembles rank
-        only the features below ``dict_size[g]``.  The mask goes through ``recon_profile(rows, max_kept=0,
-        keep=mask, budget=budget)``."""
+        only the features below ``dict_size[g]``.  ``rank_by="delta_sse"`` ranks by the exact ablation effect
+        instead (``attribution(rows).top_mask(n_top)``).  The mask goes through ``recon_profile(rows,
+        max_kept=0, keep=mask, budget=budget)``."""
         from . import sparse_recon as sr
 
-        if stats is None:
-            stats = self.feature_stats(rows)
-        mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top, self.nactive)
+        if rank_by == "delta_sse":
+            mask = self.attribution(rows, budget=budget).top_mask(n_top)
+        elif rank_by != "sum":
+            raise ValueError(f"rank_by must be 'sum' or 'delta_sse', got {rank_by!r}")
+        else:
+            if stats is None:
+                stats = self.feature_stats(rows)
+            mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top, self.nactive)
         prof = self.recon_profile(rows, max_kept=0, keep=mask, budget=budget)
         return prof.fvu_keep, prof.fvu_rest
 

@@ -181,6 +181,18 @@ class SparseCodes:
 
         return lp.label_profile(self, labels, **kw)
 
+    def attribution(self, D: torch.Tensor, x: torch.Tensor, **kw):
+        """What every feature of every model does for the reconstruction of the rows ``x`` ([n_rows, d] shared or
+        [G, n_rows, d], as the decoder sees them) from the unit-norm dictionaries ``D`` [G, n, d], an
+        ``engine.attribution.Attribution``: the exact rise of the squared error when the feature is removed
+        (``delta_sse``), the least-squares rescale of its codes and how often its firing makes a row worse
+        (keywords ``nactive``, ``feature_codes``, ``state``, ``return_proj`` of ``engine.attribution.attribution``).
+        The kernels of ``csrc/attribution.hip`` when the tensors are on a GPU (never synchronises), the torch
+        oracle elsewhere."""
+        from . import attribution as at
+
+        return at.attribution(self, D, x, **kw)
+
     @classmethod
     def cat(cls, parts: Sequence["SparseCodes"]) -> "SparseCodes":
         """The rows of ``parts`` one after the other (same models, same width).  Synchronises; needs

@@ -509,16 +509,43 @@ class FusedTopKEnsemble:
         return lp.label_profile(self.encode_sparse(rows, budget=budget), labels, **kw)
 
     @torch.no_grad()
-    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None):
+    def attribution(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None,
+                    return_proj: bool = False):
+        """What every feature of every model does for the reconstruction of ``rows`` [N, d]: an
+        ``engine.attribution.Attribution`` with the SAE engine's contract -- ``encode_sparse(rows,
+        budget=budget)`` (this engine's: from the picks), then per batch one ``residual_proj`` launch on the
+        batch's row window against the bf16 ``shadow`` of the unit-norm dictionaries, ``by_feature`` and one
+        ``attr_list_sums`` launch (``csrc/attribution.hip``), and the variance bookkeeping of ``evaluate()``;
+        ``state`` merges an earlier call.  Parameters, moments, shadows, window counts, the step counter and
+        captured graphs are left as they are."""
+        from . import attribution as at
+
+        if state is not None:
+            at.check_state(state, self.n_models, self.n, self.d)
+        codes = self.encode_sparse(rows, budget=budget)
+        B = self.batch_size
+        pool = self._x_bf16(rows)
+        batches = (pool[i:i + B] for i in range(0, rows.shape[0], B))
+        return at.attribution_fused(codes, self.shadow, batches, None, None, state, return_proj=return_proj)
+
+    @torch.no_grad()
+    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None,
+                           rank_by: str = "sum"):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` when only its ``n_top`` most
         active features are kept, and the FVU of the rest, with the SAE engine's contract: features ordered
         by the sum of their codes (``feature_stats(rows)``, or a passed ``stats``) descending, then feature
-        index ascending; the mask goes through ``recon_profile(rows, max_kept=0, keep=mask)``."""
+        index ascending -- or, with ``rank_by="delta_sse"``, by ``attribution(rows).top_mask(n_top)``; the mask
+        goes through ``recon_profile(rows, max_kept=0, keep=mask)``."""
         from . import sparse_recon as sr
 
-        if stats is None:
-            stats = self.feature_stats(rows)
-        mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top)
+        if rank_by == "delta_sse":
+            mask = self.attribution(rows, budget=budget).top_mask(n_top)
+        elif rank_by != "sum":
+            raise ValueError(f"rank_by must be 'sum' or 'delta_sse', got {rank_by!r}")
+        else:
+            if stats is None:
+                stats = self.feature_stats(rows)
+            mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top)
         prof = self.recon_profile(rows, max_kept=0, keep=mask, budget=budget)
         return prof.fvu_keep, prof.fvu_rest
 

@@ -532,23 +532,61 @@ class EnsembleTrainer:
             live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
         return lp.label_profile_reference(codes, labels, nactive=live, **kw)
 
+    # ------------------------------------------------------------------ ablation effect and shrinkage
+    def attribution(self, rows: torch.Tensor, **kw):
+        """What every feature of every model does for the reconstruction of ``rows`` [N, d]: an
+        ``engine.attribution.Attribution`` -- the exact rise of the squared error when the feature is removed,
+        the least-squares rescale of its codes, how often its firing makes a row worse (keywords ``budget`` as
+        ``encode_sparse``, ``state`` to merge an earlier call, ``return_proj``).
+
+        The fused SAE and top-k engines run their ``attribution`` (the kernels of ``csrc/attribution.hip`` over
+        their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows it is
+        given).  The analytic and eager engines with an untied / tied SAE signature run ``encode_sparse`` (the
+        oracle on their fp32 torch codes) and the torch oracle against their fp32 unit-norm dictionaries and the
+        rows each model sees (``LearnedDict.center``).  Data-parallel trainers and every other kind (top-k under
+        the eager engine included) raise ``NotImplementedError``."""
+        from . import attribution as at
+
+        if self._recon_route("attribution"):
+            return self.impl.attribution(rows.to(self.device), **kw)
+        state, return_proj = kw.pop("state", None), kw.pop("return_proj", False)
+        codes = self.encode_sparse(rows, **kw)
+        with torch.no_grad():
+            lds = self.impl.to_learned_dicts(self.device)
+            dicts = [ld.get_learned_dict().detach().float() for ld in lds]
+            x = torch.stack([ld.center(rows.to(dicts[0].device, torch.float32)) for ld in lds])
+        stacked = torch.zeros(len(dicts), codes.n, dicts[0].shape[1], device=dicts[0].device)
+        for g, D in enumerate(dicts):
+            stacked[g, :D.shape[0]] = D
+        live = [D.shape[0] for D in dicts]
+        return at.attribution_reference(codes.to(stacked.device), stacked, x, live, state=state,
+                                        return_proj=return_proj)
+
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, **kw):
         """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` [N, d] when only its ``n_top`` most
         active features are kept, and the FVU of the rest
         (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble; keywords
-        ``budget``, ``stats``).  Features are ordered by the sum of their codes descending, then feature
-        index ascending.  Routed as ``recon_profile``."""
+        ``budget``, ``stats``, ``rank_by``).  Features are ordered by the sum of their codes descending, then
+        feature index ascending; ``rank_by="delta_sse"`` orders them by their exact ablation effect
+        (``attribution(rows).top_mask(n_top)``).  Routed as ``recon_profile``."""
         from . import sparse_recon as sr
 
         if self._recon_route("fvu_top_activating"):
             return self.impl.fvu_top_activating(rows.to(self.device), n_top, **kw)
+        rank_by = kw.pop("rank_by", "sum")
         stats = kw.pop("stats", None)
-        if stats is None:
-            stats = self.feature_stats(rows)
-        sums = stats.sums[:, 0]
-        with torch.no_grad():
-            live = torch.tensor([ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)])
-        prof = self.recon_profile(rows, max_kept=0, keep=sr.top_features(sums, n_top, live), **kw)
+        if rank_by == "delta_sse":
+            mask = self.attribution(rows, **kw).top_mask(n_top)
+        elif rank_by != "sum":
+            raise ValueError(f"rank_by must be 'sum' or 'delta_sse', got {rank_by!r}")
+        else:
+            if stats is None:
+                stats = self.feature_stats(rows)
+            with torch.no_grad():
+                live = torch.tensor([ld.get_learned_dict().shape[0]
+                                     for ld in self.impl.to_learned_dicts(self.device)])
+            mask = sr.top_features(stats.sums[:, 0], n_top, live)
+        prof = self.recon_profile(rows, max_kept=0, keep=mask, **kw)
         return prof.fvu_keep, prof.fvu_rest
 
     # ------------------------------------------------------------------ nearest-atom matching

@@ -167,6 +167,29 @@ def label_selectivity(sparse_codes, labels: torch.Tensor, n_classes: int, m: int
     return pick(prof.top_label), pick(p), pick(r), pick(f)
 
 
+def ablation_effects(sparse_codes, D: torch.Tensor, x: torch.Tensor, nactive=None):
+    """``(delta_sse, delta_fvu)``, fp64 [G, n] each: the exact rise of the summed squared error, and of the FVU,
+    when feature f of model g alone is removed from the reconstruction of the rows ``x`` ([n_rows, d] shared or
+    [G, n_rows, d], as the decoder sees them) from the sparse codes of a pool (``engine.sparse_codes.
+    SparseCodes``) and the unit-norm dictionaries ``D`` [G, n, d] -- leave-one-out for all G n features from one
+    pass.  A feature that never fires reads 0; a negative value marks a feature the reconstruction is better
+    without.  From ``engine.attribution.attribution``: the kernels of ``csrc/attribution.hip`` on a GPU, the
+    torch oracle elsewhere."""
+    from ..engine.attribution import attribution
+
+    attr = attribution(sparse_codes, D, x, nactive)
+    return attr.delta_sse, attr.delta_fvu
+
+
+def feature_shrinkage(sparse_codes, D: torch.Tensor, x: torch.Tensor, nactive=None) -> torch.Tensor:
+    """fp64 [G, n]: the least-squares rescale of every feature's codes -- the factor that, applied to all codes of
+    feature f alone, lowers the squared error most.  L1-trained SAEs shrink their codes: values above 1 measure
+    by how much.  0 for a feature that never fires.  Arguments and routes as ``ablation_effects``."""
+    from ..engine.attribution import attribution
+
+    return attribution(sparse_codes, D, x, nactive).rescale
+
+
 def mutual_nearest(a: torch.Tensor, b: torch.Tensor, fused: bool | None = None
                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The pairs (i, j) with b_j the nearest atom of a_i and a_i the nearest atom of b_j: (ia, ib, cos),

@@ -38,65 +38,9 @@
 // column is in [0, lim), lim = n or min(n, nactive[g]).  All columns are checked before the first gather;
 // a gathered column is one of the checked ones.  Every store is behind the row's id < G n_rows test and
 // its own j <= J / j < 3 bound.  The only atomic is the 64-bit integer add on skipped.
-#include "common.h"
+#include "sr_rows.h"  // the layout, load / axpy / norm helpers and the skip rule (shared with attribution.hip)
 
 namespace scamd {
-
-constexpr int SR_ROWS = 4;   // rows (waves) per block
-constexpr int SR_AHEAD = 4;  // atoms the split kernel gathers ahead of their subtraction
-
-template <int P>
-struct SrLay {
-  static constexpr int V = P % 8 == 0 ? 8 : P % 4 == 0 ? 4 : P % 2 == 0 ? 2 : 1;  // elements per piece
-  static constexpr int NP = P / V;                                                // pieces per lane
-  static constexpr int W = V == 1 ? P : P / 2;                                    // 32-bit words of a packed row
-};
-
-// This lane's P elements of the bf16 row at `p`, packed as they lie in memory.
-template <int P>
-__device__ __forceinline__ void sr_load(const uint16_t* __restrict__ p, int lane, uint32_t (&w)[SrLay<P>::W]) {
-  constexpr int V = SrLay<P>::V;
-#pragma unroll
-  for (int pc = 0; pc < SrLay<P>::NP; ++pc) {
-    const uint16_t* q = p + pc * 64 * V + V * lane;
-    if constexpr (V == 8) {
-      const u32x4_t t = *reinterpret_cast<const u32x4_t*>(q);
-      w[4 * pc] = t[0], w[4 * pc + 1] = t[1], w[4 * pc + 2] = t[2], w[4 * pc + 3] = t[3];
-    } else if constexpr (V == 4) {
-      const u32x2_t t = *reinterpret_cast<const u32x2_t*>(q);
-      w[2 * pc] = t[0], w[2 * pc + 1] = t[1];
-    } else if constexpr (V == 2) {
-      w[pc] = *reinterpret_cast<const uint32_t*>(q);
-    } else {
-      w[pc] = *q;
-    }
-  }
-}
-
-// Element i (0 .. P-1) of a packed row as fp32.
-template <int P>
-__device__ __forceinline__ float sr_elem(const uint32_t (&w)[SrLay<P>::W], int i) {
-  if constexpr (SrLay<P>::V == 1) return __uint_as_float(w[i] << 16);
-  else return __uint_as_float((i & 1) ? (w[i >> 1] & 0xffff0000u) : (w[i >> 1] << 16));
-}
-
-// r <- r - c a, one fma per element.
-template <int P>
-__device__ __forceinline__ void sr_axpy(float (&r)[P], float c, const uint32_t (&a)[SrLay<P>::W]) {
-#pragma unroll
-  for (int i = 0; i < P; ++i) r[i] = fmaf(-c, sr_elem<P>(a, i), r[i]);
-}
-
-// |r|^2 over the wave: per lane ascending, then the xor butterfly 1, 2, 4, 8, 16, 32.
-template <int P>
-__device__ __forceinline__ float sr_norm2(const float (&r)[P]) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < P; ++i) s = fmaf(r[i], r[i], s);
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
 
 __device__ __forceinline__ unsigned long long sr_max64(unsigned long long v) {
 #pragma unroll
@@ -112,21 +56,6 @@ __device__ __forceinline__ unsigned long long sr_max64(unsigned long long v) {
 
 __device__ __forceinline__ unsigned long long sr_key(float c, int col) {
   return ((unsigned long long)__float_as_uint(c) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)col);
-}
-
-// The skip rule (wave-uniform result).  `col` is the model's column array.
-__device__ __forceinline__ bool sr_row_ok(long lo, long hi, long cap, int n, int lim, const int* __restrict__ col,
-                                          int lane) {
-  bool ok = lo >= 0 && hi >= lo && hi <= cap && hi - lo <= (long)n;
-  if (ok) {
-    bool bad = false;
-    for (long e = lo + lane; e < hi; e += 64) {
-      const int j = col[e];
-      bad |= (j < 0) | (j >= lim);
-    }
-    ok = __ballot(bad) == 0ull;
-  }
-  return ok;
 }
 
 template <int P>
@@ -277,37 +206,6 @@ using namespace scamd;
 
 static int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
 
-static bool bad_rows(const void* row_ptr, const void* col, const void* val, const void* D, const void* x,
-                     const void* out, const void* skipped, int G, long n_rows, int n, int d, long ldp, long row0,
-                     long cap, long x_stride) {
-  if (!row_ptr || !col || !val || !D || !x || !out || !skipped) return true;
-  if (G < 1 || n < 1 || d < 64 || d > 1024 || d % 64) return true;
-  if (n_rows < 0 || row0 < 0 || ldp < row0 + n_rows + 1 || cap < 0) return true;
-  if (x_stride != 0 && x_stride < n_rows * (long)d) return true;
-  return ((long)G * n_rows + SR_ROWS - 1) / SR_ROWS > 0x7fffffffL;
-}
-
-#define SR_DISPATCH(P_, CALL) \
-  switch (P_) {               \
-    case 1: { constexpr int P = 1; CALL; } break;   \
-    case 2: { constexpr int P = 2; CALL; } break;   \
-    case 3: { constexpr int P = 3; CALL; } break;   \
-    case 4: { constexpr int P = 4; CALL; } break;   \
-    case 5: { constexpr int P = 5; CALL; } break;   \
-    case 6: { constexpr int P = 6; CALL; } break;   \
-    case 7: { constexpr int P = 7; CALL; } break;   \
-    case 8: { constexpr int P = 8; CALL; } break;   \
-    case 9: { constexpr int P = 9; CALL; } break;   \
-    case 10: { constexpr int P = 10; CALL; } break; \
-    case 11: { constexpr int P = 11; CALL; } break; \
-    case 12: { constexpr int P = 12; CALL; } break; \
-    case 13: { constexpr int P = 13; CALL; } break; \
-    case 14: { constexpr int P = 14; CALL; } break; \
-    case 15: { constexpr int P = 15; CALL; } break; \
-    case 16: { constexpr int P = 16; CALL; } break; \
-    default: return 1;                              \
-  }
-
 extern "C" {
 
 // Rows row0 .. row0 + n_rows - 1 of the CSR (row_ptr int64 [G, ldp], col int32 [G, cap], val fp32 [G, cap])
@@ -317,7 +215,7 @@ extern "C" {
 int sc_recon_curve(const long* row_ptr, const int* col, const float* val, const void* D, const void* x,
                    const int* nactive, float* out, void* skipped, int G, long n_rows, int n, int d, int J, long ldp,
                    long row0, long cap, long x_stride, hipStream_t stream) {
-  if (bad_rows(row_ptr, col, val, D, x, out, skipped, G, n_rows, n, d, ldp, row0, cap, x_stride)) return 1;
+  if (sr_bad_rows(row_ptr, col, val, D, x, out, skipped, G, n_rows, n, d, ldp, row0, cap, x_stride)) return 1;
   if (J < 0 || J > 64) return 1;
   if (n_rows == 0) return 0;
   const unsigned blocks = (unsigned)(((long)G * n_rows + SR_ROWS - 1) / SR_ROWS);
@@ -332,7 +230,7 @@ int sc_recon_curve(const long* row_ptr, const int* col, const float* val, const 
 int sc_recon_split(const long* row_ptr, const int* col, const float* val, const void* D, const void* x,
                    const int* nactive, const void* keep, float* out, void* skipped, int G, long n_rows, int n, int d,
                    long ldp, long row0, long cap, long x_stride, hipStream_t stream) {
-  if (bad_rows(row_ptr, col, val, D, x, out, skipped, G, n_rows, n, d, ldp, row0, cap, x_stride)) return 1;
+  if (sr_bad_rows(row_ptr, col, val, D, x, out, skipped, G, n_rows, n, d, ldp, row0, cap, x_stride)) return 1;
   if (n_rows == 0) return 0;
   const unsigned blocks = (unsigned)(((long)G * n_rows + SR_ROWS - 1) / SR_ROWS);
 #define SR_SPLIT(K)                                                                                              \
