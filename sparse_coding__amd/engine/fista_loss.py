@@ -30,7 +30,9 @@ def fused_ok(models, batch_size: int, device, num_iter: int):
     n, d = models[0][0]["encoder"].shape
     if dev.type != "cuda" or not _lib.available():
         return False
-    return (batch_size % 128 == 0 and n % 128 == 0 and d % 256 == 0 and n in fista_ops.GRAM_N and n <= d
+    from ..ops.adam import row_width_supported
+
+    return (batch_size % 128 == 0 and n % 128 == 0 and row_width_supported(d) and n in fista_ops.GRAM_N and n <= d
             and num_iter >= 1)
 
 

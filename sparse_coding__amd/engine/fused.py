@@ -88,6 +88,9 @@ class FusedSAEEnsemble:
         n, d = self.n, self.d
         if B % 128 or n % 128 or d % 256:
             raise ValueError(f"fused path needs B%128==0, n%128==0, d%256==0 (got B={B}, n={n}, d={d})")
+        if not adam_ops.row_width_supported(d):
+            raise ValueError(f"fused path: the row-Adam kernels support the row widths {adam_ops.ROW_WIDTHS} "
+                             f"only (got d={d})")
         # Tied SAEs may carry a fixed affine centering x_c = ((x - t) R^T) * s per model
         # (reference sae_ensemble.py:126-131).  Non-identity centering runs as one extra
         # grouped GEMM (x R^T) plus an elementwise pass into a per-model x_c buffer; every
@@ -236,7 +239,7 @@ class FusedSAEEnsemble:
         # per-32-column b^2 partial sums (parity-double-buffered by the step counter) for |b|.
         # ``fused_tail=False`` keeps the separate kernels (A/B runs, the tail's reference in the tests)
         self._tail_ok = (bool(fused_tail) and self.kind in ("untied", "tied") and self.act == gemm_ops.ACT_RELU
-                         and not self.learned_center and n % 32 == 0 and d <= 1024)
+                         and not self.learned_center and n % 32 == 0 and adam_ops.tail_width_supported(d))
         self._bsq = torch.zeros(2, G, n // 32, device=dev) if self._tail_ok else None
         self._ticket = torch.zeros(adam_ops.TICKET_INTS, device=dev, dtype=torch.int32) if self._tail_ok else None
         self._bsq_dirty = True
@@ -549,7 +552,7 @@ class FusedSAEEnsemble:
         for k, g in upd:
             p, m, v = self.params[k], self.m[k], self.v[k]
             X = p.shape[-1]
-            if p.dim() == 2 and X % 256 == 0 and X <= 4096:
+            if p.dim() == 2 and adam_ops.row_width_supported(X):
                 # one row-Adam launch per vector set (rows = models, device step counter): the
                 # torch form below is ~10 launches of tiny elementwise kernels per vector
                 adam_ops.adam_rows([dict(p=p, g=g.contiguous(), m=m, v=v, shadow=None, norms=None, norm=False)],

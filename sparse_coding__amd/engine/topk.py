@@ -72,6 +72,9 @@ class FusedTopKEnsemble:
         n, d = self.n, self.d
         if B % 128 or n % 128 or d % 256:
             raise ValueError(f"fused top-k needs B%128==0, n%128==0, d%256==0 (B={B}, n={n}, d={d})")
+        if not adam_ops.row_width_supported(d):
+            raise ValueError(f"fused top-k: the row-Adam kernels support the row widths {adam_ops.ROW_WIDTHS} "
+                             f"only (got d={d})")
         self.params = {"dict": torch.stack([m[0]["dict"].detach().float() for m in models]).to(dev).contiguous()}
         self.m = {"dict": torch.zeros_like(self.params["dict"])}
         self.v = {"dict": torch.zeros_like(self.params["dict"])}
@@ -127,7 +130,7 @@ class FusedTopKEnsemble:
         self.g = torch.empty(G, n, d, device=dev, dtype=bf if grad_dtype == "bf16" else torch.float32)
         self.mse = torch.zeros(G, device=dev)
         # fused tail (``fused_tail=False``: Adam + torch reductions + counter increment as separate launches)
-        self._tail = bool(fused_tail) and d <= 1024
+        self._tail = bool(fused_tail) and adam_ops.tail_width_supported(d)
         self._ticket = torch.zeros(adam_ops.TICKET_INTS, device=dev, dtype=torch.int32)
         self.x_static = torch.zeros(B, d, device=dev, dtype=bf)
         self.use_graph = False

@@ -41,6 +41,10 @@ def _fused_ok(models, sig, batch_size, device) -> Tuple[bool, str]:
     n, d = p0[key].shape
     if batch_size % 128 or n % 128 or d % 256:
         return False, f"shape B={batch_size}, n={n}, d={d} not tiled by the fused kernels"
+    from ..ops.adam import ROW_WIDTHS, row_width_supported
+
+    if not row_width_supported(d):
+        return False, f"d={d} is not a row width of the row-Adam kernels {ROW_WIDTHS}"
     if sig is TopKEncoder:
         return True, "fused top-k"
     if getattr(sig, "fused_kind", None) is None:

@@ -35,6 +35,7 @@ import torch.nn.functional as F
 
 from ..models.lista import (FunctionalLISTADenoisingSAE, FunctionalResidualDenoisingSAE, shrinkage)
 from ..models.signatures import unit_rows
+from ..ops import adam as adam_ops
 
 
 # the unrolled steps' weight gradients keep the automatic block shape (256x256 here: the eight-wave
@@ -272,10 +273,8 @@ class UnrolledEnsemble:
         for k, p in self.params.items():
             g = grads[k]
             m, v = self.m[k], self.v[k]
-            if p.is_cuda and p.dim() == 3 and p.shape[-1] % 256 == 0 and p.shape[-1] <= 4096:
+            if p.is_cuda and p.dim() == 3 and adam_ops.row_width_supported(p.shape[-1]):
                 # matrices: the row-Adam kernel (one HBM pass; the torch form below is ~10)
-                from ..ops import adam as adam_ops
-
                 adam_ops.adam_rows([dict(p=p.data, g=g.contiguous(), m=m, v=v, shadow=None, norms=None, norm=False)],
                                    self.lr, self.step_count, b1, b2, self.eps)
                 continue
@@ -295,7 +294,9 @@ class UnrolledEnsemble:
     # ------------------------------------------------------------------ explicit LISTA step (GPU)
     def _fused_ok(self, B: int) -> bool:
         G, n, d = self.params["decoder"].shape
-        return (self.device.type == "cuda" and B % 128 == 0 and n % 256 == 0 and d % 256 == 0 and d <= 4096
+        # (the step's row Adam runs on [.., d] decoder rows and [.., n] encoder-side rows: both widths need a kernel)
+        return (self.device.type == "cuda" and B % 128 == 0 and n % 256 == 0 and adam_ops.row_width_supported(d)
+                and all(adam_ops.row_width_supported(self.params[k].shape[-1]) for k in self._mats)
                 and (B * n) % 1024 == 0 and (self.kind == "lista" or n <= 4096))
 
     def _shadows(self):

@@ -49,6 +49,23 @@ def _launch_policy() -> int:
     return _POLICY | store_policy.tail_bits()
 
 
+# The row widths d the row-Adam kernels are instantiated for (csrc/adam.hip: the SC_ADAM list of
+# ``sc_adam_rows``, the SC_TAIL list of the step tails), as d / 256.  The one statement of them on the
+# host: every gate on a row width asks these predicates (tests/test_step_update_cpu.py parses the lists).
+ROW_WIDTHS = tuple(256 * k for k in (1, 2, 3, 4, 6, 8, 16))
+TAIL_WIDTHS = tuple(256 * k for k in (1, 2, 3, 4))
+
+
+def row_width_supported(d: int) -> bool:
+    """Whether ``adam_rows`` has a kernel for rows of ``d`` elements."""
+    return int(d) in ROW_WIDTHS
+
+
+def tail_width_supported(d: int) -> bool:
+    """Whether ``step_tail`` / ``topk_tail`` have a kernel for rows of ``d`` elements."""
+    return int(d) in TAIL_WIDTHS
+
+
 def _vp(seq):
     return (C.c_void_p * len(seq))(*[_lib.ptr(t) for t in seq])
 
@@ -104,6 +121,8 @@ def adam_rows(sets, lr, step, b1=0.9, b2=0.999, eps=1e-8, rows_per_model=None, s
     d = shp[-1]
     nrows = sets[0]["p"].numel() // d
     n = shp[1] if len(shp) == 3 else None
+    if not row_width_supported(d):
+        raise ValueError(f"adam_rows has kernels for row widths {ROW_WIDTHS} only (got d = {d})")
     gbf16 = _check_sets(sets, "adam")
     gsize = 2 if gbf16 else 4
     for s in sets:
@@ -190,8 +209,9 @@ def step_tail(sets, lr, b1, b2, eps, step_dev, bias, bias_m, bias_v, colpart, en
             raise ValueError(f"row shard [{shp}] at row {row0} is outside the [{G} x {n}] stack")
         shp = (G, n, d)
     gbf16 = _check_sets(sets, "step_tail")
-    if len(shp) != 3 or shp[0] != G or shp[1] != n or n % 32 or d % 256 or d > 1024:
-        raise ValueError(f"step_tail needs [G, n, d] sets with n % 32 == 0, d in 256..1024 (got {shp}, bias {G}x{n})")
+    if len(shp) != 3 or shp[0] != G or shp[1] != n or n % 32 or not tail_width_supported(d):
+        raise ValueError(f"step_tail needs [G, n, d] sets with n % 32 == 0 and a row width d in {TAIL_WIDTHS} "
+                         f"(got {shp}, bias {G}x{n})")
     if tuple(bsq.shape) != (2, G, n // 32) or bsq.dtype != torch.float32 or not bsq.is_contiguous():
         raise ValueError("bsq must be contiguous fp32 [2, G, n/32]")
     if ticket.dtype != torch.int32 or ticket.numel() < TICKET_INTS or step_dev is None:
@@ -231,8 +251,8 @@ def topk_tail(p, g, m, v, shadow, norms, lr, b1, b2, eps, step_dev, row_se, mse,
                           ("g", g, torch.bfloat16 if gbf16 else torch.float32)):
         if t.dtype != want or tuple(t.shape) != (G, n, d) or not t.is_contiguous():
             raise ValueError(f"topk_tail tensor {name} must be contiguous {want} {(G, n, d)}")
-    if d % 256 or d > 1024:
-        raise ValueError(f"topk_tail needs d in 256..1024, a multiple of 256 (got {d})")
+    if not tail_width_supported(d):
+        raise ValueError(f"topk_tail has kernels for row widths {TAIL_WIDTHS} only (got d = {d})")
     if shadow.dtype != torch.bfloat16 or shadow.numel() != G * n * d or norms.numel() != G * n:
         raise ValueError("shadow must be bf16 [G, n, d] and norms [G, n]")
     if (row_se.dtype != torch.float32 or row_se.dim() != 2 or row_se.shape[0] != G or not row_se.is_contiguous()
@@ -253,4 +273,5 @@ def topk_tail(p, g, m, v, shadow, norms, lr, b1, b2, eps, step_dev, row_se, mse,
 def bias_sq_parts(bias, bsq, parity: int):
     """bsq[parity] = per-32-column sums of bias^2 (what the step tail reads as |b|^2)."""
     G, n = bias.shape
-    torch.sum(bias.view(G, n // 32, 32).square(), dim=-1, out=bsq[parity])
+    # (summed in fp64 and rounded once, like the kernels' sq_sum_32: the same fp32 value)
+    bsq[parity].copy_(bias.view(G, n // 32, 32).double().square().sum(dim=-1))

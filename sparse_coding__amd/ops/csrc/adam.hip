@@ -108,14 +108,36 @@ struct BiasArgs {
   int* step;                       // optional device step counter, advanced by loss_reduce
 };
 
+// Sums of a double over a wave (xor butterfly: every lane ends with the same bits) and over a 256-thread
+// block; `red` must hold >= 4 doubles of LDS.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ double block_sum_256_f64(double v, double* red) {
+  v = wave_sum_f64(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  const double r = red[0] + red[1] + red[2] + red[3];
+  __syncthreads();
+  return r;
+}
+
 // The loss terms of model g (one block of 256 threads): reduces the GEMM-epilogue partials to the
 // reference's loss terms and records |b| = sqrt(bs) of the pre-update bias for the bias-decay
 // term.  `bs` is the caller's block-wide sum of b^2.  Only G blocks run this, so every loop is
 // latency-bound: the loads are vectorised and the loops unrolled so one memory round trip serves
-// several iterations (was ~8 us at G = 8).
-__device__ __forceinline__ void loss_terms(const BiasArgs& a, int g, float bs, float* red) {
+// several iterations (was ~8 us at G = 8).  The sums and the terms are accumulated in fp64 and each
+// output is rounded once: a handful of blocks, nothing to gain from fp32, and the reported terms are
+// then the fp32 values nearest the exact ones whatever the number of tiles (in fp32 the tree's rounding
+// left them 1-2 ulp off: tests/test_step_update_gpu.py).
+__device__ __forceinline__ void loss_terms(const BiasArgs& a, int g, double bs, double* red) {
   const int tid = threadIdx.x;
-  float l1 = 0.f, l0 = 0.f, se = 0.f;
+  double l1 = 0., l0 = 0., se = 0.;
   const float2* ep = reinterpret_cast<const float2*>(a.enc_part) + (long)g * a.enc_tiles;
 #pragma unroll 4
   for (int t = tid; t < a.enc_tiles; t += 256) {
@@ -125,32 +147,34 @@ __device__ __forceinline__ void loss_terms(const BiasArgs& a, int g, float bs, f
   }
 #pragma unroll 4
   for (int t = tid; t < a.dec_tiles; t += 256) se += a.dec_part[(long)g * a.dec_tiles + t];
-  l1 = block_sum_256(l1, red);
-  l0 = block_sum_256(l0, red);
-  se = block_sum_256(se, red);
+  l1 = block_sum_256_f64(l1, red);
+  l0 = block_sum_256_f64(l0, red);
+  se = block_sum_256_f64(se, red);
   if (tid == 0) {
-    const float bnorm = sqrtf(bs);
-    const float l_rec = se / ((float)a.B * a.d);
-    const float l_l1 = a.l1[g] * l1 / a.B;
-    const float l_bd = a.bias_decay[g] * bnorm;
+    const double bnorm = sqrt(bs);
+    const double l_rec = se / ((double)a.B * a.d);
+    const double l_l1 = (double)a.l1[g] * l1 / a.B;
+    const double l_bd = (double)a.bias_decay[g] * bnorm;
     float* o = a.out + g * 6;
-    o[0] = l_rec + l_l1 + l_bd;
-    o[1] = l_rec;
-    o[2] = l_l1;
-    o[3] = l_bd;
-    o[4] = l0 / a.B;
-    o[5] = bnorm;
+    o[0] = (float)(l_rec + l_l1 + l_bd);
+    o[1] = (float)l_rec;
+    o[2] = (float)l_l1;
+    o[3] = (float)l_bd;
+    o[4] = (float)(l0 / a.B);
+    o[5] = (float)bnorm;  // (the bias-decay gradient of both update paths reads this fp32 value)
   }
 }
 
 // Sum of x^2 over the 32 columns of one bias block (32 lanes, every lane gets the total): the b^2 partial
 // the fused tail keeps per 32 columns, and the order in which loss_reduce_kernel sums |b|^2, so that
 // the separate kernels and the tail agree on |b| to the bit.
+// Summed in fp64 (the squares are exact there) and rounded once, so the partial is the fp32 nearest the
+// exact sum and torch can write the same value (ops/adam.py bias_sq_parts).
 __device__ __forceinline__ float sq_sum_32(float x) {
-  float sq = __fmul_rn(x, x);
+  double sq = (double)x * (double)x;
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 32);
-  return sq;
+  return (float)sq;
 }
 
 constexpr int LR_PARTS = 2048;  // loss_reduce_kernel: b^2 partials it can hold (n <= 65536)
@@ -158,12 +182,12 @@ constexpr int LR_PARTS = 2048;  // loss_reduce_kernel: b^2 partials it can hold 
 // Phase 1 (one block per model): the loss terms, with |b| summed from the bias itself -- in the fused
 // tail's order (per-32-column partials, then tail_bsq's sum over them) wherever a tail could run.
 __global__ __launch_bounds__(256) void loss_reduce_kernel(BiasArgs a) {
-  __shared__ float red[8];
+  __shared__ double red[4];
   __shared__ float part[LR_PARTS];
   const int g = blockIdx.x, tid = threadIdx.x;
   const int n = a.n;
   const float* b = a.b + (long)g * n;
-  float bs = 0.f;
+  double bs = 0.;
   if ((n & 31) == 0 && n / 32 <= LR_PARTS) {
     const int nb = n / 32;
     for (int c = tid >> 5; c < nb; c += 8) {
@@ -177,13 +201,13 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(BiasArgs a) {
 #pragma unroll 4
     for (int j = tid; j < n / 4; j += 256) {
       const float4 v = b4[j];
-      bs += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+      bs += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
     }
   } else {
 #pragma unroll 4
-    for (int j = tid; j < n; j += 256) bs += b[j] * b[j];
+    for (int j = tid; j < n; j += 256) bs += (double)b[j] * b[j];
   }
-  bs = block_sum_256(bs, red);
+  bs = block_sum_256_f64(bs, red);
   loss_terms(a, g, bs, red);
   // the step counter advances once per optimizer step; bias_adam (next launch) reads the new value
   if (tid == 0 && g == 0 && a.step) *a.step += 1;
@@ -287,35 +311,36 @@ struct TailArgs {
 
 // Block-wide sum of b^2 of model g's pre-update bias from the previous step's partials (every
 // block of the model alike).
-__device__ __forceinline__ float tail_bsq(const BiasArgs& a, const TailArgs& t, int g, int par, float* red) {
+__device__ __forceinline__ double tail_bsq(const BiasArgs& a, const TailArgs& t, int g, int par, double* red) {
   const int nb = a.n / 32;
-  float bs = 0.f;
+  double bs = 0.;
   for (int j = threadIdx.x; j < nb; j += 256) bs += t.bsq[((long)par * a.nmodels + g) * nb + j];
-  return block_sum_256(bs, red);
+  return block_sum_256_f64(bs, red);
 }
 
 __device__ __forceinline__ void tail_loss(const BiasArgs& a, const TailArgs& t, int g, int par) {
-  __shared__ float red[8];
+  __shared__ double red[4];
   loss_terms(a, g, tail_bsq(a, t, g, par, red), red);
 }
 
 __device__ __forceinline__ void tail_mse(const TailArgs& t, int g) {
-  __shared__ float red[8];
-  float se = 0.f;
+  __shared__ double red[4];
+  double se = 0.;  // (fp64, rounded once: as loss_terms)
   const float* rs = t.row_se + (long)g * t.se_rows;
 #pragma unroll 4
   for (int r = threadIdx.x; r < t.se_rows; r += 256) se += rs[r];
-  se = block_sum_256(se, red);
-  if (threadIdx.x == 0) t.mse[g] = se * t.se_scale;
+  se = block_sum_256_f64(se, red);
+  if (threadIdx.x == 0) t.mse[g] = (float)(se * (double)t.se_scale);
 }
 
 __device__ __forceinline__ void tail_bias(const BiasArgs& a, const TailArgs& t, int bx, int g, int step, int par) {
-  __shared__ float sred[8];
-  const float bs = tail_bsq(a, t, g, par, sred);
+  __shared__ double sred[4];
+  // (|b| only enters through the bias-decay term: a model without one skips the sum; block-uniform)
+  const double bs = a.bias_decay[g] != 0.f ? tail_bsq(a, t, g, par, sred) : 0.;
   float bc1, bc2;
   bias_corrections(a.b1, a.b2, step + 1, bc1, bc2);
   float bn;
-  if (!bias_adam_cols(a, g, bx, sqrtf(bs), bc1, bc2, bn)) return;
+  if (!bias_adam_cols(a, g, bx, (float)sqrt(bs), bc1, bc2, bn)) return;  // (float)sqrt: loss_terms' o[5]
   // this block's 32 columns of |b_new|^2 for the next step (lanes 0-31 of wave 0)
   const float sq = sq_sum_32(bn);
   if (threadIdx.x == 0) t.bsq[((long)(par ^ 1) * a.nmodels + g) * (a.n / 32) + bx] = sq;

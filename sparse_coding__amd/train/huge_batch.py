@@ -36,6 +36,7 @@ from ..data.chunks import ChunkFolder
 from ..data.ring import DeviceRing
 from ..models.learned_dict import LearnedDict
 from ..models.signatures import FunctionalSAE
+from ..ops.adam import row_width_supported
 from ..parallel.dist import DistInfo, init_distributed
 from ..utils.config import BaseArgs, _default_device
 from ..utils.logging import Logger
@@ -166,7 +167,7 @@ class HugeBatchTrainer:
         torch.manual_seed(cfg.seed)
         n = cfg.n_features
         fused_ok = (self.device.type == "cuda" and not cfg.tied and cfg.batch_size % 128 == 0 and n % 128 == 0
-                    and d % 256 == 0)
+                    and d % 256 == 0 and row_width_supported(d))
         eng = cfg.engine if cfg.engine != "auto" else ("fused" if fused_ok else "torch")
         if eng == "fused" and not fused_ok:
             raise ValueError("fused engine needs a GPU, an untied SAE and B%128, n%128, d%256 == 0")
