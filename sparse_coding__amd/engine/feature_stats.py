@@ -131,6 +131,26 @@ def empty_topk(G: int, n: int, K: int, device=None):
             torch.full((G, n, K), -1, dtype=torch.int64, device=device))
 
 
+def open_accumulators(state: Optional[FeatureStats], G: int, n: int, topk: int, device, max0: float):
+    """``(acc, mx, tv, tr, seen)`` of an engine's ``feature_stats`` loop, fresh or continuing ``state``: ``acc``
+    fp64 [G, 5, n] (count, sum c .. sum c^4), ``mx`` fp32 [G, n] starting at ``max0`` (what a feature that
+    never fires reads: -inf from a dense reduction, 0 from the picks), the top-K lists (``topk`` > 0) and the
+    rows already seen.  Copies of the state's tensors: the state itself is left as it is."""
+    tv = tr = None
+    if state is None:
+        acc = torch.zeros(G, 5, n, device=device, dtype=torch.float64)
+        mx = torch.full((G, n), max0, device=device)
+        if topk:
+            tv, tr = empty_topk(G, n, topk, device)
+        return acc, mx, tv, tr, 0
+    acc = torch.cat([state.count.to(device, torch.float64).unsqueeze(1), state.sums.to(device)], dim=1).contiguous()
+    mx = state.max.to(device, copy=True).contiguous()
+    if topk:
+        tv = state.top_vals.to(device, copy=True).contiguous()
+        tr = state.top_rows.to(device, copy=True).contiguous()
+    return acc, mx, tv, tr, int(state.n_rows)
+
+
 def merge_topk_reference(top_vals: torch.Tensor, top_rows: torch.Tensor, c: torch.Tensor, row0: int):
     """The top-K merge on its own: the lists [G, n, K] after the batch of codes ``c`` [G, B, n] with global
     rows ``row0 .. row0 + B - 1``.  Previous entries first, then the candidates in row order, one stable

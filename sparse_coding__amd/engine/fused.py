@@ -40,6 +40,7 @@ import torch
 
 from ..ops import adam as adam_ops
 from ..ops import gemm as gemm_ops
+from .analysis import CodeAnalyses
 
 
 # engine kind -> code activation of the encoder / code-gradient epilogues
@@ -59,7 +60,7 @@ def _stack(models, key, which=0, device=None):
     return torch.stack([m[which][key].detach().float() for m in models]).to(device).contiguous()
 
 
-class FusedSAEEnsemble:
+class FusedSAEEnsemble(CodeAnalyses):
     """Fused HIP training engine; API mirrors ``FunctionalEnsemble``."""
 
     def __init__(self, models, sig, lr=1e-3, batch_size=256, device="cuda", betas=(0.9, 0.999),
@@ -858,12 +859,8 @@ class FusedSAEEnsemble:
         if why is not None:
             raise NotImplementedError(f"resample_dead: {why}")
         rs._check(rule, pick)
-        B, G, n, d = self.batch_size, self.n_models, self.n, self.d
-        if rows.dim() != 2 or rows.shape[1] != d:
-            raise ValueError(f"rows must be [N, {d}], got {tuple(rows.shape)}")
-        N = rows.shape[0]
-        if N <= 0 or N % B:
-            raise ValueError(f"the pool needs a positive multiple of the batch size ({B}) rows, got {N}")
+        N = self._check_rows(rows, "the pool")
+        B, G, n = self.batch_size, self.n_models, self.n
         dev = self.device
         pool = self._x_bf16(rows)
         bias = self.params[self._bkey]
@@ -902,14 +899,32 @@ class FusedSAEEnsemble:
         self._bsq_dirty = True
         return cnt
 
-    def _stats_unsupported(self) -> Optional[str]:
-        if self.kind == "threshold":
-            return "threshold SAEs: the codes are not a ReLU of the encoder's pre-activation"
-        if self.kind == "reverse":
-            return "reverse SAEs: the bias-subtracted codes are not a ReLU of the encoder's pre-activation"
-        if self.learned_center:
-            return "learned centering is not covered"
-        return None
+    # ------------------------------------------------------------------ sparse codes and their analyses
+    # (``interference`` .. ``atom_matches`` are ``CodeAnalyses``', engine/analysis.py, on the hooks below)
+    def _analysis_refusal(self, what: str) -> None:
+        """Reads ``kind`` and ``learned_center`` alone: it comes before anything else is touched."""
+        why = None
+        if what == "atom_matches":
+            if self.kind not in ("untied", "tied"):
+                why = f"no unit-norm dictionary shadow for {self.kind} SAEs"
+        elif self.kind == "threshold":
+            why = "threshold SAEs: the codes are not a ReLU of the encoder's pre-activation"
+        elif self.kind == "reverse":
+            why = "reverse SAEs: the bias-subtracted codes are not a ReLU of the encoder's pre-activation"
+        elif self.learned_center:
+            why = "learned centering is not covered"
+        if why is not None:
+            raise NotImplementedError(f"{what}: {why}")
+
+    def _dictionaries(self):
+        return self.dec_shadow  # (the encoder shadow of tied models)
+
+    def _live_counts(self):
+        return self.nactive
+
+    def _decoder_batches(self, rows):
+        B, pool = self.batch_size, self._x_bf16(rows)
+        return (self.prepare(pool[i:i + B]) for i in range(0, rows.shape[0], B))
 
     @torch.no_grad()
     def feature_stats(self, rows: torch.Tensor, *, topk: int = 0, row_offset: int = 0, state=None):
@@ -931,34 +946,15 @@ class FusedSAEEnsemble:
         from ..ops import feature_stats as fs_ops
         from . import feature_stats as fs
 
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"feature_stats: {why}")
-        B, G, n, d = self.batch_size, self.n_models, self.n, self.d
-        if rows.dim() != 2 or rows.shape[1] != d:
-            raise ValueError(f"rows must be [N, {d}], got {tuple(rows.shape)}")
-        N = rows.shape[0]
-        if N <= 0 or N % B:
-            raise ValueError(f"feature_stats needs a positive multiple of the batch size ({B}) rows, got {N}")
+        self._analysis_refusal("feature_stats")
+        N = self._check_rows(rows, "feature_stats")
+        B, G, n = self.batch_size, self.n_models, self.n
         topk, row_offset = fs.check_request(topk, row_offset, state, G, n)
         dev = self.device
         part = getattr(self, "_stats_part", None)
         if part is None:
             part = self._stats_part = torch.empty(G, fs_ops.moment_slabs(G, B, n), fs_ops.N_STATS, n, device=dev)
-        tv = tr = None
-        if state is None:
-            acc = torch.zeros(G, 5, n, device=dev, dtype=torch.float64)  # count, sum c .. sum c^4
-            mx = torch.full((G, n), float("-inf"), device=dev)
-            if topk:
-                tv, tr = fs.empty_topk(G, n, topk, dev)
-            seen = 0
-        else:
-            acc = torch.cat([state.count.to(dev, torch.float64).unsqueeze(1), state.sums.to(dev)], dim=1)
-            mx = state.max.to(dev, copy=True)
-            if topk:
-                tv = state.top_vals.to(dev, copy=True).contiguous()
-                tr = state.top_rows.to(dev, copy=True).contiguous()
-            seen = int(state.n_rows)
+        acc, mx, tv, tr, seen = fs.open_accumulators(state, G, n, topk, dev, float("-inf"))
         pool = self._x_bf16(rows)
         for i in range(0, N, B):
             self._encode_only(self.prepare(pool[i:i + B]))
@@ -989,15 +985,9 @@ class FusedSAEEnsemble:
         from ..ops import sparse_codes as sc_ops
         from . import sparse_codes as sc
 
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"encode_sparse: {why}")
-        B, G, n, d = self.batch_size, self.n_models, self.n, self.d
-        if rows.dim() != 2 or rows.shape[1] != d:
-            raise ValueError(f"rows must be [N, {d}], got {tuple(rows.shape)}")
-        N = rows.shape[0]
-        if N <= 0 or N % B:
-            raise ValueError(f"encode_sparse needs a positive multiple of the batch size ({B}) rows, got {N}")
+        self._analysis_refusal("encode_sparse")
+        N = self._check_rows(rows, "encode_sparse")
+        B, G, n = self.batch_size, self.n_models, self.n
         cap = sc.check_budget(budget, N, n)
         dev = self.device
         pool = self._x_bf16(rows)
@@ -1019,209 +1009,6 @@ class FusedSAEEnsemble:
                 sc_ops.extend_row_ptr(row_ptr, nnz, i)
             sc_ops.code_compact(self.c, row_ptr, col, val, i)
         return sc.SparseCodes(N, n, row_ptr, col, val)
-
-    @torch.no_grad()
-    def interference(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None):
-        """Expected interference of every feature of every model on ``rows`` [N, d] (N a positive multiple
-        of the batch size): an ``engine.interference.Interference`` whose ``expected`` [G, n] is the
-        activity-weighted capacity ``c_a / sum_b cos^2(a, b) c_b`` averaged over the rows on which the
-        feature fires (``eval.metrics.calc_expected_interference``), and ``capacity`` the static capacity.
-
-        ``encode_sparse(rows, budget=budget)`` under its budget contract (``budget=int`` never
-        synchronises, ``None`` synchronises once), then ONE ``active_capacity`` launch over the result
-        (``csrc/interference.hip``) against the unit-norm bf16 shadow that ``atom_matches`` reads: the
-        cosines are those of the bf16-rounded dictionaries.  With a ``budget`` that is too small the rows
-        whose entries were dropped are left out and counted in ``skipped`` (``check()`` raises).
-        ``state``: the result of an earlier call to continue -- integer sums: chunk by chunk gives the
-        bits of one call on the whole pool.  Masked ensembles: atoms at or past ``dict_size[g]`` take no
-        part.  Parameters, moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and
-        captured graphs are left as they are."""
-        from . import interference as ic
-
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"interference: {why}")
-        if state is not None:
-            ic.check_state(state, self.n_models, self.n)
-        return ic.interference_fused(self.encode_sparse(rows, budget=budget), self.dec_shadow, self.nactive, state)
-
-    @torch.no_grad()
-    def recon_profile(self, rows: torch.Tensor, *, max_kept: int = 32, keep=None, budget: Optional[int] = None,
-                      state=None):
-        """Truncated and ablated reconstruction error of every model on ``rows`` [N, d] (N a positive
-        multiple of the batch size): an ``engine.sparse_recon.ReconProfile`` whose ``fvu_prefix`` [G, J + 1]
-        is the FVU when only the j largest codes of every row are kept (j = 0 .. ``max_kept`` <= 64; equal
-        codes go to the lower feature index), ``fvu_full`` the FVU from all codes and -- with ``keep``, a
-        bool [G, n] feature mask or its ``keep_words`` -- ``fvu_keep`` / ``fvu_rest`` the FVU from the kept
-        features' codes and from the others'.
-
-        ``encode_sparse(rows, budget=budget)`` under its budget contract, then per batch ``prepare()``, one
-        ``recon_curve`` and one ``recon_split`` launch on the batch's row window (``csrc/sparse_recon.hip``)
-        against the unit-norm bf16 shadow that ``interference`` reads, and the variance bookkeeping of
-        ``evaluate()``; the per-row values are summed in fp64.  With a ``budget`` that is too small the rows
-        whose entries were dropped are left out and counted in ``skipped`` (``check()`` raises).  ``state``:
-        the result of an earlier call to continue -- chunk by chunk gives the bits of one call on the whole
-        pool.  Tied models with a fixed affine centering are measured in the centred space, as
-        ``evaluate()``.  Parameters, moments, shadows, ``feature_counts``, ``rows_seen``, the step counter
-        and captured graphs are left as they are."""
-        from . import sparse_recon as sr
-
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"recon_profile: {why}")
-        J = sr.check_max_kept(max_kept)
-        if state is not None:
-            sr.check_state(state, self.n_models, J, keep is not None, self.d)
-        codes = self.encode_sparse(rows, budget=budget)
-        B = self.batch_size
-        pool = self._x_bf16(rows)
-        batches = (self.prepare(pool[i:i + B]) for i in range(0, rows.shape[0], B))
-        return sr.recon_profile_fused(codes, self.dec_shadow, batches, J, keep, self.nactive, state)
-
-    @torch.no_grad()
-    def feature_examples(self, rows: torch.Tensor, fragment_len: int = 64, n_top: int = 20, n_random: int = 20,
-                         seed: int = 0, budget: Optional[int] = None):
-        """Feature-major codes and example fragments of every feature of every model on ``rows`` [N, d] (N a
-        positive multiple of the batch size and of ``fragment_len``; row i is token ``i % fragment_len`` of
-        fragment ``i // fragment_len``): an ``engine.feature_codes.FeatureCodes`` and its ``FragmentExamples``
-        -- per feature the ``n_top`` fragments with the largest maximum code (ties to the lower fragment) and
-        a hash sample of ``n_random`` fragments on which it fires (both in 0..32).
-
-        ``encode_sparse(rows, budget=budget)`` under its budget contract, then the transposition and one walk
-        over every feature's list (``csrc/feature_codes.hip``); no dense codes.  With a ``budget`` that is too
-        small the rows whose entries were dropped are left out whole and counted in ``skipped`` (``check()``
-        raises).  Masked ensembles: features at or past ``dict_size[g]`` have empty lists.  Parameters,
-        moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as
-        they are."""
-        from . import feature_codes as fc
-
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"feature_examples: {why}")
-        fc.check_fragments(rows.shape[0], fragment_len)
-        return fc.feature_examples(self.encode_sparse(rows, budget=budget), self.nactive, fragment_len, n_top,
-                                   n_random, seed)
-
-    @torch.no_grad()
-    def coactivation(self, rows: torch.Tensor, *, m: int = 4, score: str = "pearson", min_both: int = 1,
-                     budget: Optional[int] = None):
-        """Co-activation partners across the models of the ensemble on ``rows`` [N, d] (N a positive multiple of
-        the batch size): an ``engine.coactivation.CoActivation`` holding, for every ordered pair (g, h), the
-        ``m`` (0..32) features of model h that fire with each feature of model g on at least ``min_both`` rows
-        and score best (``score``: "pearson", "cosine" or "jaccard" of their codes; for g == h the best *other*
-        features): what the atoms alone cannot tell -- feature splitting, or two close atoms that fire on
-        different rows.
-
-        ``encode_sparse(rows, budget=budget)`` under its budget contract, then the transposition, the list
-        moments and one walk per (feature, model) over the feature's list (``csrc/coactivation.hip``); no dense
-        codes and no [n, n] matrix.  With a ``budget`` that is too small the rows whose entries were dropped are
-        left out whole and counted in ``skipped_a`` / ``skipped_b`` (``check()`` raises).  Masked ensembles:
-        features at or past ``dict_size[g]`` have no partners and are nobody's.  There is no ``state=``: the m
-        best of a sum cannot be merged across chunks, so the pool is given whole.  Parameters, moments,
-        shadows, ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as they are."""
-        from . import coactivation as co
-
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"coactivation: {why}")
-        return co.coactivation(self.encode_sparse(rows, budget=budget), m=m, score=score, min_both=min_both,
-                               nactive_a=self.nactive)
-
-    @torch.no_grad()
-    def label_profile(self, rows: torch.Tensor, labels: torch.Tensor, *, budget: Optional[int] = None, **kw):
-        """Per feature of every model the labels that carry its activations on ``rows`` [N, d] (N a positive
-        multiple of the batch size): an ``engine.label_profile.LabelProfile``.  ``labels`` int32 / int64 [N]
-        gives every row a label -- its token id, its position, a concept flag; a negative one leaves the row out
-        -- and the profile holds per feature its ``m`` best labels by ``rank_by`` with their counts, fp64 sums
-        and maxima, and the totals that turn them into shares, precision and recall (keywords ``m``,
-        ``rank_by``, ``n_classes`` of ``engine.label_profile.label_profile``).
-
-        ``encode_sparse(rows, budget=budget)`` under its budget contract, the kept rows gathered in label order
-        (``SparseCodes.take_rows``), the transposition and one walk per feature list
-        (``csrc/label_profile.hip``); no dense codes and no global sort of the entries.  The codes must be
-        complete: a ``budget`` that is too small raises ``SparseCodesOverflow``.  Masked ensembles: features at
-        or past ``dict_size[g]`` have empty profiles.  Parameters, moments, shadows, ``feature_counts``,
-        ``rows_seen``, the step counter and captured graphs are left as they are."""
-        from . import label_profile as lp
-
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"label_profile: {why}")
-        return lp.label_profile(self.encode_sparse(rows, budget=budget), labels, nactive=self.nactive, **kw)
-
-    @torch.no_grad()
-    def attribution(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None,
-                    return_proj: bool = False):
-        """What every feature of every model does for the reconstruction of ``rows`` [N, d] (N a positive
-        multiple of the batch size): an ``engine.attribution.Attribution`` whose ``delta_sse`` [G, n] is the
-        exact rise of the summed squared error when the feature alone is removed, ``rescale`` the least-squares
-        factor on its codes (the shrinkage diagnostic of L1-trained SAEs), ``harmful_fraction`` how often its
-        firing makes its row worse, and ``top_mask(k)`` a keep mask for ``recon_profile``.
-
-        ``encode_sparse(rows, budget=budget)`` under its budget contract, then per batch ``prepare()`` and one
-        ``residual_proj`` launch on the batch's row window against the unit-norm bf16 shadow that
-        ``recon_profile`` reads, then ``by_feature`` and one ``attr_list_sums`` launch
-        (``csrc/attribution.hip``), and the variance bookkeeping of ``evaluate()``.  With a ``budget`` that is
-        too small the rows whose entries were dropped are left out and counted in ``skipped`` (``check()``
-        raises).  ``state``: the result of an earlier call to merge with (``Attribution.merge``).
-        ``return_proj``: keep the per-entry projections, aligned with the codes' ``col`` / ``val``.  Tied models
-        with a fixed affine centering are measured in the centred space.  Parameters, moments, shadows,
-        ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as they are."""
-        from . import attribution as at
-
-        why = self._stats_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"attribution: {why}")
-        if state is not None:
-            at.check_state(state, self.n_models, self.n, self.d)
-        codes = self.encode_sparse(rows, budget=budget)
-        B = self.batch_size
-        pool = self._x_bf16(rows)
-        batches = (self.prepare(pool[i:i + B]) for i in range(0, rows.shape[0], B))
-        return at.attribution_fused(codes, self.dec_shadow, batches, self.nactive, None, state,
-                                    return_proj=return_proj)
-
-    @torch.no_grad()
-    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None,
-                           rank_by: str = "sum"):
-        """FVU of every model on ``rows`` when only its ``n_top`` most active features are kept, and the FVU
-        of the rest (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble):
-        (fvu_top [G], fvu_rest [G]) in fp64 on the device.  The features are ordered by the sum of their
-        codes on ``rows`` descending, then feature index ascending -- from ``feature_stats(rows)``, or from
-        ``stats``, an earlier ``FeatureStats`` of the same rows, to save that pass; masked ensembles rank
-        only the features below ``dict_size[g]``.  ``rank_by="delta_sse"`` ranks by the exact ablation effect
-        instead (``attribution(rows).top_mask(n_top)``).  The mask goes through ``recon_profile(rows,
-        max_kept=0, keep=mask, budget=budget)``."""
-        from . import sparse_recon as sr
-
-        if rank_by == "delta_sse":
-            mask = self.attribution(rows, budget=budget).top_mask(n_top)
-        elif rank_by != "sum":
-            raise ValueError(f"rank_by must be 'sum' or 'delta_sse', got {rank_by!r}")
-        else:
-            if stats is None:
-                stats = self.feature_stats(rows)
-            mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top, self.nactive)
-        prof = self.recon_profile(rows, max_kept=0, keep=mask, budget=budget)
-        return prof.fvu_keep, prof.fvu_rest
-
-    @torch.no_grad()
-    def atom_matches(self, m: int = 1):
-        """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` holding, for
-        every ordered pair (g, h), the ``m`` (1..8) nearest atoms of model h for each atom of model g (cosine
-        descending, lowest index among equal cosines), and for g == h the nearest *other* atoms.
-
-        Reads the bf16 shadow that holds the unit-norm dictionaries in place (the decoder shadow of untied
-        models, the encoder shadow of tied ones): the matches are those of the bf16-rounded dictionaries.
-        G launches of G problems per pass on the row-argmax epilogue of the grouped GEMM
-        (``ops.gemm.rowargmax_nt``).  Masked ensembles: atoms at or past ``dict_size[g]`` read (0.0, -1)
-        and are never a match.  Never synchronises; parameters, moments, shadows, counts, the step
-        counter and captured graphs are left as they are."""
-        from . import atom_match as am
-
-        if self.kind not in ("untied", "tied"):
-            raise NotImplementedError(f"atom_matches: no unit-norm dictionary shadow for {self.kind} SAEs")
-        return am.atom_matches_fused(self.dec_shadow, self.nactive, m)
 
     def feature_frequency(self) -> torch.Tensor:
         """Per-feature firing frequency [G, n] = feature_counts / rows_seen.  The counts are SAMPLED:

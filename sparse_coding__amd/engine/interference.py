@@ -4,9 +4,10 @@ The activity-weighted capacity of Scherlis et al. 2022 (reference big_sweep.py:4
 feature a with code c_a gets ``c_a / sum_b cos^2(a, b) c_b`` over the row's active features b, and the
 expected interference of a feature is the mean of that value over the rows on which it fires.  A row
 needs only the Gram matrix of its own active atoms, so the sparse codes of ``encode_sparse`` are the
-natural input: ``FusedSAEEnsemble.interference`` / ``FusedTopKEnsemble.interference`` run one
-``ops.interference.active_capacity`` launch over them; ``active_capacity_reference`` computes the same
-sums in fp64 torch (CPU included) and is what the tests compare against.
+natural input: ``CodeAnalyses.interference`` (``engine/analysis.py``) runs one
+``ops.interference.active_capacity`` launch over them on the fused engines (``interference_fused``);
+``active_capacity_reference`` computes the same sums in fp64 torch (CPU included) and is what the tests
+compare against and what the analytic / eager engines run (``interference_reference``).
 
 Per-entry capacities are quantised to multiples of 2^-32 and summed as int64, so the per-feature sums
 are the same bits every run and under any split of the pool.
@@ -170,6 +171,17 @@ def live_counts(nactive, G: int, n: int, device) -> Optional[torch.Tensor]:
     if t.numel() != G:
         raise ValueError(f"nactive must hold one count per model ({G}), got {t.numel()}")
     return t.clamp(0, n).contiguous()
+
+
+def interference_reference(sparse_codes: SparseCodes, D: torch.Tensor, nactive=None,
+                           state: Optional[Interference] = None) -> Interference:
+    """The ``Interference`` of ``sparse_codes`` against the dictionaries ``D`` [G, n, d] from the fp64 oracle
+    (any device, any float dtype), merged into ``state`` when one is continued."""
+    from ..eval.metrics import capacity_per_feature_lowrank
+
+    ref = active_capacity_reference(sparse_codes.to(D.device), D, nactive)
+    out = Interference(sparse_codes.n_rows, ref.qsum, ref.count, ref.skipped, capacity_per_feature_lowrank(D, nactive))
+    return out if state is None else state.merge(out)
 
 
 def interference_fused(sparse_codes: SparseCodes, shadow: torch.Tensor, nactive=None,

@@ -388,7 +388,8 @@ def top_features(sums: torch.Tensor, n_top: int, live=None) -> torch.Tensor:
     s = sums.double()
     alive = None
     if live is not None:
-        alive = torch.arange(n, device=sums.device).unsqueeze(0) < live.to(sums.device).reshape(-1, 1)
+        live = torch.as_tensor(live).to(sums.device)
+        alive = torch.arange(n, device=sums.device).unsqueeze(0) < live.reshape(-1, 1)
         s = torch.where(alive, s, torch.full_like(s, float("-inf")))
     order = torch.argsort(s, dim=1, descending=True, stable=True)
     mask = torch.zeros(G, n, dtype=torch.bool, device=sums.device)

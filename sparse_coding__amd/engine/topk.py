@@ -43,6 +43,7 @@ from ..ops import adam as adam_ops
 from ..ops import gemm as gemm_ops
 from ..ops import topk as topk_ops
 from ..ops import topk_stats as tstats_ops
+from .analysis import CodeAnalyses
 
 # Cost model of the weight gradient per model (MI355X, measured on config 4): the slot-list
 # kernel moves ~4 d bytes per pick at ~5 TB/s from L2 / MALL; the dense two-segment GEMM does
@@ -58,7 +59,7 @@ def auto_sparse_k(B: int, n: int, d: int, margin: float = 1.3) -> int:
     return int(dense / (per_k * margin))
 
 
-class FusedTopKEnsemble:
+class FusedTopKEnsemble(CodeAnalyses):
     def __init__(self, models, sig=None, lr=1e-3, batch_size=256, device="cuda", betas=(0.9, 0.999), eps=1e-8,
                  grad_dtype: str = "bf16", sparse_k: Union[int, str] = "auto", scores_dtype: Optional[str] = None,
                  fused_tail: bool = True, count_every: int = 0):
@@ -287,13 +288,14 @@ class FusedTopKEnsemble:
             topk_ops.decode_grad(idx, val, self.k, self.shadow, x, self.r, self.row_se, None, None)
         return idx, val
 
-    def _check_rows(self, rows, what: str):
-        if rows.dim() != 2 or rows.shape[1] != self.d:
-            raise ValueError(f"rows must be [N, {self.d}], got {tuple(rows.shape)}")
-        N = rows.shape[0]
-        if N <= 0 or N % self.batch_size:
-            raise ValueError(f"{what} needs a positive multiple of the batch size ({self.batch_size}) rows, got {N}")
-        return N
+    # the hooks of ``CodeAnalyses`` (engine/analysis.py: ``interference`` .. ``atom_matches``).  Nothing is
+    # refused and nothing is masked; the decoder reads the pool's bf16 rows as they are
+    def _dictionaries(self):
+        return self.shadow
+
+    def _decoder_batches(self, rows):
+        B, pool = self.batch_size, self._x_bf16(rows)
+        return (pool[i:i + B] for i in range(0, rows.shape[0], B))
 
     @torch.no_grad()
     def evaluate(self, rows: torch.Tensor):
@@ -389,20 +391,7 @@ class FusedTopKEnsemble:
         topk, row_offset = fs.check_request(topk, row_offset, state, G, n)
         if self._stat_lists is None:
             self._stat_lists = topk_ops.SlotLists(G, B, n, self._ks, self.kmax, dev)
-        tv = tr = None
-        if state is None:
-            acc = torch.zeros(G, 5, n, device=dev, dtype=torch.float64)  # count, sum c .. sum c^4
-            mx = torch.zeros(G, n, device=dev)
-            if topk:
-                tv, tr = fs.empty_topk(G, n, topk, dev)
-            seen = 0
-        else:
-            acc = torch.cat([state.count.to(dev, torch.float64).unsqueeze(1), state.sums.to(dev)], dim=1).contiguous()
-            mx = state.max.to(dev, copy=True).contiguous()
-            if topk:
-                tv = state.top_vals.to(dev, copy=True).contiguous()
-                tr = state.top_rows.to(dev, copy=True).contiguous()
-            seen = int(state.n_rows)
+        acc, mx, tv, tr, seen = fs.open_accumulators(state, G, n, topk, dev, 0.0)
         pool = self._x_bf16(rows)
         for i in range(0, N, B):
             idx, val = self._forward_only(pool[i:i + B], decode=False)
@@ -436,132 +425,6 @@ class FusedTopKEnsemble:
                 yield idx, val  # (consumed before the next batch overwrites the pick buffers)
 
         return sc.sparse_codes_from_picks(picks(), self.k, self.n, cap)
-
-    @torch.no_grad()
-    def interference(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None):
-        """Expected interference of every feature of every model on ``rows`` [N, d]: an
-        ``engine.interference.Interference`` with the SAE engine's contract -- ``encode_sparse(rows,
-        budget=budget)`` (this engine's: from the picks), then one ``active_capacity`` launch over the
-        result against the bf16 ``shadow`` of the unit-norm dictionaries; ``state`` continues an earlier
-        call with the bits of one call on the whole pool.  Parameters, moments, shadows, window counts,
-        the step counter and captured graphs are left as they are."""
-        from . import interference as ic
-
-        if state is not None:
-            ic.check_state(state, self.n_models, self.n)
-        return ic.interference_fused(self.encode_sparse(rows, budget=budget), self.shadow, None, state)
-
-    @torch.no_grad()
-    def recon_profile(self, rows: torch.Tensor, *, max_kept: int = 32, keep=None, budget: Optional[int] = None,
-                      state=None):
-        """Truncated and ablated reconstruction error of every model on ``rows`` [N, d]: an
-        ``engine.sparse_recon.ReconProfile`` with the SAE engine's contract -- ``encode_sparse(rows,
-        budget=budget)`` (this engine's: from the picks), then per batch one ``recon_curve`` and one
-        ``recon_split`` launch on the batch's row window against the bf16 ``shadow`` of the unit-norm
-        dictionaries, and the variance bookkeeping of ``evaluate()``; ``state`` continues an earlier call
-        with the bits of one call on the whole pool.  Parameters, moments, shadows, window counts, the step
-        counter and captured graphs are left as they are."""
-        from . import sparse_recon as sr
-
-        J = sr.check_max_kept(max_kept)
-        if state is not None:
-            sr.check_state(state, self.n_models, J, keep is not None, self.d)
-        codes = self.encode_sparse(rows, budget=budget)
-        B = self.batch_size
-        pool = self._x_bf16(rows)
-        batches = (pool[i:i + B] for i in range(0, rows.shape[0], B))
-        return sr.recon_profile_fused(codes, self.shadow, batches, J, keep, None, state)
-
-    @torch.no_grad()
-    def feature_examples(self, rows: torch.Tensor, fragment_len: int = 64, n_top: int = 20, n_random: int = 20,
-                         seed: int = 0, budget: Optional[int] = None):
-        """Feature-major codes and example fragments of every feature of every model on ``rows`` [N, d]: an
-        ``engine.feature_codes.FeatureCodes`` and its ``FragmentExamples`` with the SAE engine's contract --
-        ``encode_sparse(rows, budget=budget)`` (this engine's: from the picks), the transposition and one walk
-        over every feature's list (``csrc/feature_codes.hip``).  Parameters, moments, shadows, window counts,
-        the step counter and captured graphs are left as they are."""
-        from . import feature_codes as fc
-
-        fc.check_fragments(rows.shape[0], fragment_len)
-        return fc.feature_examples(self.encode_sparse(rows, budget=budget), None, fragment_len, n_top, n_random,
-                                   seed)
-
-    @torch.no_grad()
-    def coactivation(self, rows: torch.Tensor, *, m: int = 4, score: str = "pearson", min_both: int = 1,
-                     budget: Optional[int] = None):
-        """Co-activation partners across the models of the ensemble on ``rows`` [N, d]: an
-        ``engine.coactivation.CoActivation`` with the SAE engine's contract -- ``encode_sparse(rows,
-        budget=budget)`` (this engine's: from the picks), the transposition, the list moments and one walk per
-        (feature, model) over the feature's list (``csrc/coactivation.hip``).  There is no ``state=``: the pool
-        is given whole.  Parameters, moments, shadows, window counts, the step counter and captured graphs are
-        left as they are."""
-        from . import coactivation as co
-
-        return co.coactivation(self.encode_sparse(rows, budget=budget), m=m, score=score, min_both=min_both)
-
-    @torch.no_grad()
-    def label_profile(self, rows: torch.Tensor, labels: torch.Tensor, *, budget: Optional[int] = None, **kw):
-        """Per feature of every model the labels that carry its activations on ``rows`` [N, d]: an
-        ``engine.label_profile.LabelProfile`` with the SAE engine's contract -- ``encode_sparse(rows,
-        budget=budget)`` (this engine's: from the picks), the kept rows gathered in label order, the
-        transposition and one walk per feature list (``csrc/label_profile.hip``; keywords ``m``, ``rank_by``,
-        ``n_classes``).  Parameters, moments, shadows, window counts, the step counter and captured graphs are
-        left as they are."""
-        from . import label_profile as lp
-
-        return lp.label_profile(self.encode_sparse(rows, budget=budget), labels, **kw)
-
-    @torch.no_grad()
-    def attribution(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None,
-                    return_proj: bool = False):
-        """What every feature of every model does for the reconstruction of ``rows`` [N, d]: an
-        ``engine.attribution.Attribution`` with the SAE engine's contract -- ``encode_sparse(rows,
-        budget=budget)`` (this engine's: from the picks), then per batch one ``residual_proj`` launch on the
-        batch's row window against the bf16 ``shadow`` of the unit-norm dictionaries, ``by_feature`` and one
-        ``attr_list_sums`` launch (``csrc/attribution.hip``), and the variance bookkeeping of ``evaluate()``;
-        ``state`` merges an earlier call.  Parameters, moments, shadows, window counts, the step counter and
-        captured graphs are left as they are."""
-        from . import attribution as at
-
-        if state is not None:
-            at.check_state(state, self.n_models, self.n, self.d)
-        codes = self.encode_sparse(rows, budget=budget)
-        B = self.batch_size
-        pool = self._x_bf16(rows)
-        batches = (pool[i:i + B] for i in range(0, rows.shape[0], B))
-        return at.attribution_fused(codes, self.shadow, batches, None, None, state, return_proj=return_proj)
-
-    @torch.no_grad()
-    def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, *, budget: Optional[int] = None, stats=None,
-                           rank_by: str = "sum"):
-        """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` when only its ``n_top`` most
-        active features are kept, and the FVU of the rest, with the SAE engine's contract: features ordered
-        by the sum of their codes (``feature_stats(rows)``, or a passed ``stats``) descending, then feature
-        index ascending -- or, with ``rank_by="delta_sse"``, by ``attribution(rows).top_mask(n_top)``; the mask
-        goes through ``recon_profile(rows, max_kept=0, keep=mask)``."""
-        from . import sparse_recon as sr
-
-        if rank_by == "delta_sse":
-            mask = self.attribution(rows, budget=budget).top_mask(n_top)
-        elif rank_by != "sum":
-            raise ValueError(f"rank_by must be 'sum' or 'delta_sse', got {rank_by!r}")
-        else:
-            if stats is None:
-                stats = self.feature_stats(rows)
-            mask = sr.top_features(stats.sums[:, 0].to(self.device), n_top)
-        prof = self.recon_profile(rows, max_kept=0, keep=mask, budget=budget)
-        return prof.fvu_keep, prof.fvu_rest
-
-    @torch.no_grad()
-    def atom_matches(self, m: int = 1):
-        """Nearest atoms across the models of the ensemble: an ``engine.atom_match.AtomMatches`` with the
-        SAE engine's contract (``m`` in 1..8; for g == h the nearest *other* atoms; lowest index among
-        equal cosines).  Reads the bf16 ``shadow`` of the unit-norm dictionaries in place; never
-        synchronises and leaves parameters, moments, shadows, window counts, the step counter and
-        captured graphs as they are."""
-        from . import atom_match as am
-
-        return am.atom_matches_fused(self.shadow, None, m)
 
     def state_dict(self):
         """Masters, moments and the step; with ``count_every > 0`` also the window counts."""

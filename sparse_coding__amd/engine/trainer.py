@@ -23,6 +23,7 @@ from ..models.fista import FistaDictUpdater, FunctionalFista
 from ..models.signatures import unit_rows
 from ..models.topk import TopKEncoder
 from . import analytic, unrolled
+from .analysis import TorchCodeAnalyses
 from .ensemble import FunctionalEnsemble
 from .optim import adam
 
@@ -323,302 +324,86 @@ class EnsembleTrainer:
         cnt = rs.resample_stacked(impl.params, m, v, rows, kind, live=live, **kw)
         return [int(c) for c in cnt.cpu()]
 
-    # ------------------------------------------------------------------ per-feature statistics
-    def feature_stats(self, rows: torch.Tensor, **kw):
-        """Per-feature activation statistics of every model on ``rows`` [N, d]: an
-        ``engine.feature_stats.FeatureStats`` (keywords ``topk``, ``row_offset``, ``state``).
-
-        The fused SAE engine runs ``FusedSAEEnsemble.feature_stats`` (N a multiple of its batch size;
-        under ensemble sharding each rank gets the statistics of its own models on the rows it is given,
-        N a multiple of the engine's global batch).  The fused top-k engine runs
-        ``FusedTopKEnsemble.feature_stats`` (from the picks, no dense codes).  The analytic and eager
-        engines with an untied / tied SAE signature run the fp64 oracle on their fp32 torch codes,
-        ``batch_size`` rows at a time.  Data-parallel trainers and every other kind (top-k under the
-        eager engine included) raise ``NotImplementedError``."""
-        from . import feature_stats as fs
-
-        if self.dp is not None:
-            raise NotImplementedError("feature_stats: data-parallel replicas (parallel='dp'/'zero1') hold the same "
-                                      "models on different rows; collect the statistics on one rank's engine")
-        if self.kind in ("fused-sae", "fused-topk"):
-            return self.impl.feature_stats(rows.to(self.device), **kw)
-        kind = analytic._KINDS.get(self.sig)
-        if self.kind not in ("analytic", "eager") or kind is None:
-            raise NotImplementedError(f"feature_stats: no code path for the {self.kind} engine with "
-                                      f"{getattr(self.sig, '__name__', self.sig)}")
-        impl = self.impl
-        d = impl.params["encoder"].shape[-1]
-        if rows.dim() != 2 or rows.shape[1] != d or rows.shape[0] < 1:
-            raise ValueError(f"rows must be [N, {d}] with N >= 1, got {tuple(rows.shape)}")
-        buffers = getattr(impl, "buffers", {})
-        with torch.no_grad():
-            codes = (fs.stacked_codes(impl.params, buffers, kind, rows[i:i + self.batch_size])
-                     for i in range(0, rows.shape[0], self.batch_size))
-            return fs.feature_stats_reference(codes, **kw)
-
-    # ------------------------------------------------------------------ sparse codes
-    def encode_sparse(self, rows: torch.Tensor, **kw):
-        """The codes of every model on ``rows`` [N, d] as an ``engine.sparse_codes.SparseCodes``: per-model
-        CSR of the strictly positive codes (keyword ``budget``: entries per row the buffers hold, or
-        ``None`` to size them exactly with one synchronisation).
-
-        The fused SAE and top-k engines run their ``encode_sparse`` (N a multiple of the batch size; under
-        ensemble sharding each rank gets the codes of its own models on the rows it is given, N a multiple
-        of the engine's global batch).  The analytic and eager engines with an untied / tied SAE signature
-        run the oracle on their fp32 torch codes, ``batch_size`` rows at a time.  Data-parallel trainers
+    # ------------------------------------------------------------------ sparse codes and their analyses
+    def _analyses(self, what: str):
+        """The provider of ``what``, one of the sparse-code analyses (``engine/analysis.py``): the fused SAE
+        or top-k engine (under ensemble sharding: this rank's models on the rows it is given), or the torch
+        route of the analytic and eager engines with an untied / tied SAE signature.  Data-parallel trainers
         and every other kind (top-k under the eager engine included) raise ``NotImplementedError``."""
-        from . import feature_stats as fs
-        from . import sparse_codes as sc
-
-        if self.dp is not None:
-            raise NotImplementedError("encode_sparse: data-parallel replicas (parallel='dp'/'zero1') hold the same "
-                                      "models on different rows; encode on one rank's engine")
-        if self.kind in ("fused-sae", "fused-topk"):
-            return self.impl.encode_sparse(rows.to(self.device), **kw)
-        kind = analytic._KINDS.get(self.sig)
-        if self.kind not in ("analytic", "eager") or kind is None:
-            raise NotImplementedError(f"encode_sparse: no code path for the {self.kind} engine with "
-                                      f"{getattr(self.sig, '__name__', self.sig)}")
-        impl = self.impl
-        n, d = impl.params["encoder"].shape[-2:]
-        if rows.dim() != 2 or rows.shape[1] != d or rows.shape[0] < 1:
-            raise ValueError(f"rows must be [N, {d}] with N >= 1, got {tuple(rows.shape)}")
-        cap = sc.check_budget(kw.pop("budget", None), rows.shape[0], n)
-        if kw:
-            raise TypeError(f"encode_sparse: unexpected keywords {sorted(kw)}")
-        buffers = getattr(impl, "buffers", {})
-        with torch.no_grad():
-            codes = (fs.stacked_codes(impl.params, buffers, kind, rows[i:i + self.batch_size])
-                     for i in range(0, rows.shape[0], self.batch_size))
-            return sc.sparse_codes_reference(codes, cap)
-
-    # ------------------------------------------------------------------ expected interference
-    def interference(self, rows: torch.Tensor, **kw):
-        """Expected interference of every feature of every model on ``rows`` [N, d]: an
-        ``engine.interference.Interference`` (keywords ``budget`` as ``encode_sparse``, ``state`` to continue
-        an earlier call).
-
-        The fused SAE and top-k engines run their ``interference`` (the ``active_capacity`` kernel over
-        their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows
-        it is given).  The analytic and eager engines with an untied / tied SAE signature run
-        ``encode_sparse`` (the oracle on their fp32 torch codes) and the fp64 oracle against their fp32
-        unit-norm dictionaries.  Data-parallel trainers and every other kind (top-k under the eager engine
-        included) raise ``NotImplementedError``."""
-        from ..eval.metrics import capacity_per_feature_lowrank
-        from . import interference as ic
-
-        if self.dp is not None:
-            raise NotImplementedError("interference: data-parallel replicas (parallel='dp'/'zero1') hold the same "
-                                      "models on different rows; collect it on one rank's engine")
-        if self.kind in ("fused-sae", "fused-topk"):
-            return self.impl.interference(rows.to(self.device), **kw)
-        if self.kind not in ("analytic", "eager") or analytic._KINDS.get(self.sig) is None:
-            raise NotImplementedError(f"interference: no code path for the {self.kind} engine with "
-                                      f"{getattr(self.sig, '__name__', self.sig)}")
-        state = kw.pop("state", None)
-        codes = self.encode_sparse(rows, **kw)
-        with torch.no_grad():
-            dicts = [ld.get_learned_dict().detach().float() for ld in self.impl.to_learned_dicts(self.device)]
-        stacked = torch.zeros(len(dicts), codes.n, dicts[0].shape[1], device=dicts[0].device)
-        for g, D in enumerate(dicts):
-            stacked[g, :D.shape[0]] = D
-        live = [D.shape[0] for D in dicts]
-        ref = ic.active_capacity_reference(codes.to(stacked.device), stacked, live)
-        out =ic.Interference(codes.n_rows, ref.qsum, ref.count, ref.skipped,
-                              capacity_per_feature_lowrank(stacked, live))
-        return out if state is None else state.merge(out)
-
-    # ------------------------------------------------------------------ truncated / ablated reconstruction
-    def _recon_route(self, what: str):
-        """True for the fused engines, False for the torch route; raises for everything else."""
         if self.dp is not None:
             raise NotImplementedError(f"{what}: data-parallel replicas (parallel='dp'/'zero1') hold the same "
                                       "models on different rows; collect it on one rank's engine")
         if self.kind in ("fused-sae", "fused-topk"):
-            return True
-        if self.kind not in ("analytic", "eager") or analytic._KINDS.get(self.sig) is None:
+            return self.impl
+        kind = analytic._KINDS.get(self.sig)
+        if self.kind not in ("analytic", "eager") or kind is None:
             raise NotImplementedError(f"{what}: no code path for the {self.kind} engine with "
                                       f"{getattr(self.sig, '__name__', self.sig)}")
-        return False
+        return TorchCodeAnalyses(self.impl, kind, self.batch_size, self.device)
+
+    def feature_stats(self, rows: torch.Tensor, **kw):
+        """Per-feature activation statistics of every model on ``rows`` [N, d]: an
+        ``engine.feature_stats.FeatureStats`` (keywords ``topk``, ``row_offset``, ``state``).  The fused
+        engines' ``feature_stats`` (N a multiple of the batch size), or the fp64 oracle on the torch route's
+        fp32 codes, ``batch_size`` rows at a time (N >= 1); routed by ``_analyses``."""
+        return self._analyses("feature_stats").feature_stats(rows.to(self.device), **kw)
+
+    def encode_sparse(self, rows: torch.Tensor, **kw):
+        """The codes of every model on ``rows`` [N, d] as an ``engine.sparse_codes.SparseCodes``: per-model
+        CSR of the strictly positive codes (keyword ``budget``: entries per row the buffers hold, or ``None``
+        to size them exactly with one synchronisation).  The fused engines' ``encode_sparse`` (N a multiple
+        of the batch size), or the oracle on the torch route's fp32 codes (N >= 1); routed by ``_analyses``."""
+        return self._analyses("encode_sparse").encode_sparse(rows.to(self.device), **kw)
+
+    def interference(self, rows: torch.Tensor, **kw):
+        """``CodeAnalyses.interference`` of the engine (keywords ``budget``, ``state``); routed by ``_analyses``."""
+        return self._analyses("interference").interference(rows.to(self.device), **kw)
 
     def recon_profile(self, rows: torch.Tensor, **kw):
-        """Truncated and ablated reconstruction error of every model on ``rows`` [N, d]: an
-        ``engine.sparse_recon.ReconProfile`` (keywords ``max_kept``, ``keep``, ``budget`` as
-        ``encode_sparse``, ``state`` to continue an earlier call).
+        """``CodeAnalyses.recon_profile`` of the engine (keywords ``max_kept``, ``keep``, ``budget``, ``state``);
+        routed by ``_analyses``."""
+        return self._analyses("recon_profile").recon_profile(rows.to(self.device), **kw)
 
-        The fused SAE and top-k engines run their ``recon_profile`` (the ``recon_curve`` / ``recon_split``
-        kernels over their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models
-        on the rows it is given).  The analytic and eager engines with an untied / tied SAE signature run
-        ``encode_sparse`` (the oracle on their fp32 torch codes) and the fp64 oracle against their fp32
-        unit-norm dictionaries and the rows each model sees (``LearnedDict.center``).  Data-parallel
-        trainers and every other kind (top-k under the eager engine included) raise
-        ``NotImplementedError``."""
-        from . import sparse_recon as sr
-
-        if self._recon_route("recon_profile"):
-            return self.impl.recon_profile(rows.to(self.device), **kw)
-        state, keep, max_kept = kw.pop("state", None), kw.pop("keep", None), kw.pop("max_kept", 32)
-        codes = self.encode_sparse(rows, **kw)
-        with torch.no_grad():
-            lds = self.impl.to_learned_dicts(self.device)
-            dicts = [ld.get_learned_dict().detach().float() for ld in lds]
-            x = torch.stack([ld.center(rows.to(dicts[0].device, torch.float32)) for ld in lds])
-        stacked = torch.zeros(len(dicts), codes.n, dicts[0].shape[1], device=dicts[0].device)
-        for g, D in enumerate(dicts):
-            stacked[g, :D.shape[0]] = D
-        live = [D.shape[0] for D in dicts]
-        return sr.recon_profile_reference(codes.to(stacked.device), stacked, x, max_kept, keep, live, state)
-
-    # ------------------------------------------------------------------ feature-major codes and example fragments
     def feature_examples(self, rows: torch.Tensor, **kw):
-        """Feature-major codes and example fragments of every feature of every model on ``rows`` [N, d]: an
-        ``engine.feature_codes.FeatureCodes`` and its ``FragmentExamples`` (keywords ``fragment_len``, ``n_top``,
-        ``n_random``, ``seed``, ``budget`` as ``encode_sparse``).
+        """``CodeAnalyses.feature_examples`` of the engine (keywords ``fragment_len``, ``n_top``, ``n_random``,
+        ``seed``, ``budget``); routed by ``_analyses``."""
+        return self._analyses("feature_examples").feature_examples(rows.to(self.device), **kw)
 
-        The fused SAE and top-k engines run their ``feature_examples`` (the kernels of
-        ``csrc/feature_codes.hip`` over their own ``encode_sparse``; under ensemble sharding each rank gets this
-        rank's models on the rows it is given).  The analytic and eager engines with an untied / tied SAE
-        signature run ``encode_sparse`` (the oracle on their fp32 torch codes) and the torch oracles.
-        Data-parallel trainers and every other kind (top-k under the eager engine included) raise
-        ``NotImplementedError``."""
-        from . import feature_codes as fc
-
-        if self._recon_route("feature_examples"):
-            return self.impl.feature_examples(rows.to(self.device), **kw)
-        budget = kw.pop("budget", None)
-        fc.check_fragments(rows.shape[0], kw.get("fragment_len", 64))
-        codes = self.encode_sparse(rows, budget=budget)
-        with torch.no_grad():
-            live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
-        feats = fc.feature_codes_reference(codes, live)
-        return feats, fc.fragment_examples_reference(feats, **kw)
-
-    # ------------------------------------------------------------------ co-activation partners
     def coactivation(self, rows: torch.Tensor, **kw):
-        """Co-activation partners across the models on ``rows`` [N, d]: an ``engine.coactivation.CoActivation``
-        -- for every ordered pair (g, h) the features of model h that fire on the same rows as each feature of
-        model g and score best (keywords ``m``, ``score``, ``min_both``, ``budget`` as ``encode_sparse``).  There
-        is no ``state=``: the pool is given whole.
+        """``CodeAnalyses.coactivation`` of the engine (keywords ``m``, ``score``, ``min_both``, ``budget``; no
+        ``state=``: the pool is given whole); routed by ``_analyses``."""
+        return self._analyses("coactivation").coactivation(rows.to(self.device), **kw)
 
-        The fused SAE and top-k engines run their ``coactivation`` (the kernels of ``csrc/coactivation.hip`` over
-        their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows it is
-        given).  The analytic and eager engines with an untied / tied SAE signature run ``encode_sparse`` (the
-        oracle on their fp32 torch codes) and the torch oracle.  Data-parallel trainers and every other kind
-        (top-k under the eager engine included) raise ``NotImplementedError``."""
-        from . import coactivation as co
-
-        if self._recon_route("coactivation"):
-            return self.impl.coactivation(rows.to(self.device), **kw)
-        budget = kw.pop("budget", None)
-        codes = self.encode_sparse(rows, budget=budget)
-        with torch.no_grad():
-            live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
-        return co.coactivation_reference(codes, nactive_a=live, **kw)
-
-    # ------------------------------------------------------------------ label profiles
     def label_profile(self, rows: torch.Tensor, labels: torch.Tensor, **kw):
-        """Per feature of every model the labels that carry its activations on ``rows`` [N, d]: an
-        ``engine.label_profile.LabelProfile`` (``labels`` int32 / int64 [N], negative: the row is left out;
-        keywords ``m``, ``rank_by``, ``n_classes``, ``budget`` as ``encode_sparse``).
+        """``CodeAnalyses.label_profile`` of the engine (``labels`` int32 / int64 [N], negative: the row is left
+        out; keywords ``m``, ``rank_by``, ``n_classes``, ``budget``); routed by ``_analyses``."""
+        return self._analyses("label_profile").label_profile(rows.to(self.device), labels.to(self.device), **kw)
 
-        The fused SAE and top-k engines run their ``label_profile`` (the kernels of ``csrc/label_profile.hip``
-        over their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows
-        it is given).  The analytic and eager engines with an untied / tied SAE signature run ``encode_sparse``
-        (the oracle on their fp32 torch codes) and the torch oracle.  Data-parallel trainers and every other
-        kind (top-k under the eager engine included) raise ``NotImplementedError``."""
-        from . import label_profile as lp
-
-        if self._recon_route("label_profile"):
-            return self.impl.label_profile(rows.to(self.device), labels.to(self.device), **kw)
-        budget = kw.pop("budget", None)
-        codes = self.encode_sparse(rows, budget=budget)
-        with torch.no_grad():
-            live = [ld.get_learned_dict().shape[0] for ld in self.impl.to_learned_dicts(self.device)]
-        return lp.label_profile_reference(codes, labels, nactive=live, **kw)
-
-    # ------------------------------------------------------------------ ablation effect and shrinkage
     def attribution(self, rows: torch.Tensor, **kw):
-        """What every feature of every model does for the reconstruction of ``rows`` [N, d]: an
-        ``engine.attribution.Attribution`` -- the exact rise of the squared error when the feature is removed,
-        the least-squares rescale of its codes, how often its firing makes a row worse (keywords ``budget`` as
-        ``encode_sparse``, ``state`` to merge an earlier call, ``return_proj``).
-
-        The fused SAE and top-k engines run their ``attribution`` (the kernels of ``csrc/attribution.hip`` over
-        their own ``encode_sparse``; under ensemble sharding each rank gets this rank's models on the rows it is
-        given).  The analytic and eager engines with an untied / tied SAE signature run ``encode_sparse`` (the
-        oracle on their fp32 torch codes) and the torch oracle against their fp32 unit-norm dictionaries and the
-        rows each model sees (``LearnedDict.center``).  Data-parallel trainers and every other kind (top-k under
-        the eager engine included) raise ``NotImplementedError``."""
-        from . import attribution as at
-
-        if self._recon_route("attribution"):
-            return self.impl.attribution(rows.to(self.device), **kw)
-        state, return_proj = kw.pop("state", None), kw.pop("return_proj", False)
-        codes = self.encode_sparse(rows, **kw)
-        with torch.no_grad():
-            lds = self.impl.to_learned_dicts(self.device)
-            dicts = [ld.get_learned_dict().detach().float() for ld in lds]
-            x = torch.stack([ld.center(rows.to(dicts[0].device, torch.float32)) for ld in lds])
-        stacked = torch.zeros(len(dicts), codes.n, dicts[0].shape[1], device=dicts[0].device)
-        for g, D in enumerate(dicts):
-            stacked[g, :D.shape[0]] = D
-        live = [D.shape[0] for D in dicts]
-        return at.attribution_reference(codes.to(stacked.device), stacked, x, live, state=state,
-                                        return_proj=return_proj)
+        """``CodeAnalyses.attribution`` of the engine (keywords ``budget``, ``state``, ``return_proj``); routed by
+        ``_analyses``."""
+        return self._analyses("attribution").attribution(rows.to(self.device), **kw)
 
     def fvu_top_activating(self, rows: torch.Tensor, n_top: int = 2, **kw):
-        """(fvu_top [G], fvu_rest [G]): the FVU of every model on ``rows`` [N, d] when only its ``n_top`` most
-        active features are kept, and the FVU of the rest
-        (``eval.metrics.fraction_variance_unexplained_top_activating`` for the whole ensemble; keywords
-        ``budget``, ``stats``, ``rank_by``).  Features are ordered by the sum of their codes descending, then
-        feature index ascending; ``rank_by="delta_sse"`` orders them by their exact ablation effect
-        (``attribution(rows).top_mask(n_top)``).  Routed as ``recon_profile``."""
-        from . import sparse_recon as sr
+        """``CodeAnalyses.fvu_top_activating`` of the engine: (fvu_top [G], fvu_rest [G]) (keywords ``budget``,
+        ``stats``, ``rank_by``); routed by ``_analyses``."""
+        return self._analyses("fvu_top_activating").fvu_top_activating(rows.to(self.device), n_top, **kw)
 
-        if self._recon_route("fvu_top_activating"):
-            return self.impl.fvu_top_activating(rows.to(self.device), n_top, **kw)
-        rank_by = kw.pop("rank_by", "sum")
-        stats = kw.pop("stats", None)
-        if rank_by == "delta_sse":
-            mask = self.attribution(rows, **kw).top_mask(n_top)
-        elif rank_by != "sum":
-            raise ValueError(f"rank_by must be 'sum' or 'delta_sse', got {rank_by!r}")
-        else:
-            if stats is None:
-                stats = self.feature_stats(rows)
-            with torch.no_grad():
-                live = torch.tensor([ld.get_learned_dict().shape[0]
-                                     for ld in self.impl.to_learned_dicts(self.device)])
-            mask = sr.top_features(stats.sums[:, 0], n_top, live)
-        prof = self.recon_profile(rows, max_kept=0, keep=mask, **kw)
-        return prof.fvu_keep, prof.fvu_rest
-
-    # ------------------------------------------------------------------ nearest-atom matching
     def atom_matches(self, m: int = 1):
-        """Nearest atoms across the models: an ``engine.atom_match.AtomMatches`` -- for every ordered pair
-        (g, h) the ``m`` nearest atoms of model h for each atom of model g, for g == h the nearest other
-        atoms; lowest index among equal cosines.
-
-        The fused SAE and top-k engines run their ``atom_matches`` on the bf16 shadows (under ensemble
-        sharding: this rank's models; graphed data-parallel replicas: the local engine, the models are
-        the same on every rank).  The analytic and eager engines with an SAE or top-k signature run the
-        fp64 oracle on their unstacked fp32 dictionaries.  Every other kind (the unrolled and
-        FISTA-in-the-loss engines) raises ``NotImplementedError``."""
-        from . import atom_match as am
-
+        """``CodeAnalyses.atom_matches``: the nearest atoms across the models, with a wider routing than the
+        analyses of codes, since only the dictionaries are read.  The fused SAE and top-k engines match their
+        bf16 shadows (under ensemble sharding: this rank's models; graphed data-parallel replicas: the local
+        engine, the models are the same on every rank).  The analytic and eager engines, data-parallel ones
+        included, with an SAE or top-k signature run the fp64 oracle on their fp32 dictionaries.  Every other
+        kind (the unrolled and FISTA-in-the-loss engines) raises ``NotImplementedError``."""
         if self.kind in ("fused-sae", "fused-topk") or self.kind.endswith("-graphed"):
             return self.impl.atom_matches(m)
         sae = self.sig in analytic._KINDS or self.sig is TopKEncoder
         if not (self.kind in ("analytic", "eager") or self.kind.endswith("-eager")) or not sae:
             raise NotImplementedError(f"atom_matches: no unit-norm dictionary to match for the {self.kind} engine "
                                       f"with {getattr(self.sig, '__name__', self.sig)}")
-        with torch.no_grad():
-            dicts = [ld.get_learned_dict().detach().float() for ld in self.impl.to_learned_dicts(self.device)]
-        n = max(D.shape[0] for D in dicts)
-        stacked = torch.zeros(len(dicts), n, dicts[0].shape[1], device=dicts[0].device)
-        for g, D in enumerate(dicts):
-            stacked[g, :D.shape[0]] = D
-        return am.atom_matches_reference(stacked, [D.shape[0] for D in dicts], m, True)
+        return TorchCodeAnalyses(self.impl, analytic._KINDS.get(self.sig), self.batch_size,
+                                 self.device).atom_matches(m)
 
     # ------------------------------------------------------------------ export / state
     def hyperparams(self, ensemble_hyperparams: Sequence[str] = (), buffer_hyperparams: Sequence[str] = ("l1_alpha",),
