@@ -1,8 +1,9 @@
 """The analyses on top of ``encode_sparse``, written once for every engine that has sparse codes.
 
 ``CodeAnalyses`` is a mixin: ``interference``, ``recon_profile``, ``feature_examples``, ``coactivation``,
-``label_profile``, ``attribution``, ``fvu_top_activating`` and ``atom_matches`` are each one composition of
-``encode_sparse`` with the route of its module (``engine/interference.py`` .. ``engine/atom_match.py``).  A
+``label_profile``, ``value_order``, ``feature_auroc``, ``attribution``, ``fvu_top_activating`` and ``atom_matches``
+are each one composition of ``encode_sparse`` with the route of its module (``engine/interference.py`` ..
+``engine/atom_match.py``).  A
 provider keeps what really differs between engines:
 
 * ``encode_sparse(rows, *, budget=None)`` and ``feature_stats(rows, ...)``: its own loops over the pool;
@@ -182,6 +183,49 @@ class CodeAnalyses:
         codes = self.encode_sparse(rows, budget=budget)
         route = lp.label_profile if self._kernels else lp.label_profile_reference
         return route(codes, labels, nactive=self._live_counts(), **kw)
+
+    @torch.no_grad()
+    def value_order(self, rows: torch.Tensor, *, budget: Optional[int] = None):
+        """Every feature's activations on ``rows`` [N, d] (N a positive multiple of the batch size) in value
+        order: an ``engine.value_order.ValueOrdered`` -- per model and feature the rows on which it fires with
+        their codes, smallest code first -- whose ``quantiles(Q)``, ``histogram(edges)`` and
+        ``strata(n_strata, per_stratum)`` say how the activations are distributed and which rows are typical of
+        every range, by index arithmetic on the device.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, then the transposition and one
+        segmented sort, one wave per list (``csrc/value_order.hip``); no dense codes and no global sort of the
+        entries.  With a ``budget`` that is too small the rows whose entries were dropped are left out whole and
+        counted in ``skipped`` (``check()`` raises).  Masked ensembles: features at or past ``dict_size[g]`` have
+        empty lists, so their quantiles are NaN.  There is no ``state=``: an order cannot be merged across
+        chunks, so the pool is given whole.  Parameters, moments, shadows, ``feature_counts``, ``rows_seen``,
+        the step counter and captured graphs are left as they are."""
+        from . import value_order as vo
+
+        self._analysis_refusal("value_order")
+        codes = self.encode_sparse(rows, budget=budget)
+        return vo.value_order(codes, self._live_counts(), kernels=self._kernels)
+
+    @torch.no_grad()
+    def feature_auroc(self, rows: torch.Tensor, flags: torch.Tensor, *, n_concepts: Optional[int] = None,
+                      budget: Optional[int] = None):
+        """How well every feature of every model detects each of up to 32 concepts on ``rows`` [N, d] (N a
+        positive multiple of the batch size), thresholded at any level: an ``engine.value_order.FeatureAuroc``
+        whose ``auroc()`` [G, n, K] is the exact AUROC of the feature's code as a score for the concept, ties
+        counting half, and ``best(m)`` the m best features per concept.  ``flags``: int32 words [N], bit k set
+        where the row is a positive of concept k (``n_concepts`` of them, default 32), or a bool [N, K] matrix.
+        Every row counts; a row on which the feature does not fire scores 0.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, the transposition, the segmented sort
+        and one walk per value-ordered list with integer sums (``csrc/value_order.hip``).  The codes must be
+        complete: a ``budget`` that is too small raises ``SparseCodesOverflow``.  Masked ensembles: features at
+        or past ``dict_size[g]`` have empty lists and read exactly 0.5.  There is no ``state=``.  Parameters,
+        moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as
+        they are."""
+        from . import value_order as vo
+
+        self._analysis_refusal("feature_auroc")
+        codes = self.encode_sparse(rows, budget=budget)
+        return vo.feature_auroc(codes, flags, n_concepts, self._live_counts(), kernels=self._kernels)
 
     @torch.no_grad()
     def attribution(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None,

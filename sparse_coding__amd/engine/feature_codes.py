@@ -191,6 +191,15 @@ class FeatureCodes:
                                         frags.contiguous(), f0)
         return fragment_acts_reference(self, fragment_len, frags, f0)
 
+    def by_value(self, **kw):
+        """These lists in value order, an ``engine.value_order.ValueOrdered``: every list ordered by the key of
+        its codes ascending, then row ascending, at its own positions -- what quantiles, strata, histograms and
+        the per-feature AUROC are read from.  One launch of the segmented sort of ``csrc/value_order.hip`` on a
+        GPU (``kw``: its ``waves``; never synchronises), the oracle elsewhere."""
+        from . import value_order as vo
+
+        return vo.by_value(self, **kw)
+
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
         return {"n_rows": torch.tensor(int(self.n_rows), dtype=torch.int64),

@@ -112,6 +112,11 @@ class SparseCodes:
 
         return fc.by_feature(self, nactive, **kw)
 
+    def by_value(self, nactive=None):
+        """``by_feature(nactive).by_value()``: every feature's list in value order, an
+        ``engine.value_order.ValueOrdered`` with its ``quantiles``, ``histogram``, ``strata`` and ``auroc``."""
+        return self.by_feature(nactive).by_value()
+
     def coactivation(self, other: Optional["SparseCodes"] = None, **kw):
         """The best co-activation partners of every feature of every model among the features of every model of
         ``other`` (default: these codes themselves), an ``engine.coactivation.CoActivation``: which features

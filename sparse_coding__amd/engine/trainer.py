@@ -379,6 +379,16 @@ class EnsembleTrainer:
         out; keywords ``m``, ``rank_by``, ``n_classes``, ``budget``); routed by ``_analyses``."""
         return self._analyses("label_profile").label_profile(rows.to(self.device), labels.to(self.device), **kw)
 
+    def value_order(self, rows: torch.Tensor, **kw):
+        """``CodeAnalyses.value_order`` of the engine (keyword ``budget``; no ``state=``: the pool is given whole);
+        routed by ``_analyses``."""
+        return self._analyses("value_order").value_order(rows.to(self.device), **kw)
+
+    def feature_auroc(self, rows: torch.Tensor, flags: torch.Tensor, **kw):
+        """``CodeAnalyses.feature_auroc`` of the engine (``flags`` int32 words [N] or bool [N, K]; keywords
+        ``n_concepts``, ``budget``); routed by ``_analyses``."""
+        return self._analyses("feature_auroc").feature_auroc(rows.to(self.device), flags.to(self.device), **kw)
+
     def attribution(self, rows: torch.Tensor, **kw):
         """``CodeAnalyses.attribution`` of the engine (keywords ``budget``, ``state``, ``return_proj``); routed by
         ``_analyses``."""

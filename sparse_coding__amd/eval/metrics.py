@@ -167,6 +167,28 @@ def label_selectivity(sparse_codes, labels: torch.Tensor, n_classes: int, m: int
     return pick(prof.top_label), pick(p), pick(r), pick(f)
 
 
+def activation_quantiles(sparse_codes, Q: int, nactive=None) -> torch.Tensor:
+    """fp32 [G, n, Q + 1]: quantiles of every feature's activations over the rows on which it fires, from the
+    sparse codes of a pool (``engine.sparse_codes.SparseCodes``): entry k is the value at sorted position
+    ``(k (L - 1)) // Q`` of the feature's L codes (k = 0 the smallest, k = Q the largest); NaN for a feature
+    that never fires.  From ``SparseCodes.by_value``: the segmented sort of ``csrc/value_order.hip`` on a GPU,
+    the torch oracle elsewhere."""
+    return sparse_codes.by_value(nactive).quantiles(Q)
+
+
+def feature_auroc(sparse_codes, flags: torch.Tensor, nactive=None, n_concepts=None) -> torch.Tensor:
+    """fp64 [G, n, K]: the exact AUROC of every feature's activation as a score for each of K <= 32 concepts over
+    all rows of a pool, ties counting half, from its complete sparse codes (``engine.sparse_codes.SparseCodes``).
+    ``flags``: int32 words [n_rows] whose bit k marks the positives of concept k (``n_concepts`` of them, default
+    32), or a bool [n_rows, K] matrix.  A row on which the feature does not fire scores 0; a feature that never
+    fires reads 0.5; a concept with no positive or no negative reads NaN.  The per-feature counterpart of probing
+    a whole dictionary with a logistic regression.  From ``engine.value_order.feature_auroc``: the kernels of
+    ``csrc/value_order.hip`` on a GPU, the torch oracle elsewhere."""
+    from ..engine.value_order import feature_auroc as route
+
+    return route(sparse_codes, flags, n_concepts, nactive).auroc()
+
+
 def ablation_effects(sparse_codes, D: torch.Tensor, x: torch.Tensor, nactive=None):
     """``(delta_sse, delta_fvu)``, fp64 [G, n] each: the exact rise of the summed squared error, and of the FVU,
     when feature f of model g alone is removed from the reconstruction of the rows ``x`` ([n_rows, d] shared or

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Callable, Iterator, List, Optional, Sequence
+from typing import Callable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -356,6 +356,42 @@ def ensemble_token_profiles(lm: HookedLM, trainer, layer: int, layer_loc: str, f
     labels = torch.full((n_pad,), -1, dtype=torch.int64)
     labels[:F * L] = token_labels(fragments.cpu(), context, ignore)
     return trainer.label_profile(rows, labels, m=m, rank_by=rank_by, n_classes=n_classes, budget=budget)
+
+
+def concept_flags(tokens: torch.Tensor, concepts) -> Tuple[torch.Tensor, List[str]]:
+    """Flag words for ``ValueOrdered.auroc`` / ``trainer.feature_auroc`` from token ids: ``concepts`` maps up to 32
+    concept names to the token ids that make a row a positive of the concept.  Returns ``(flags int32 [numel],
+    names)``: bit k of word r is set when token r (``tokens`` of any shape, in row order) is one of the ids of
+    ``names[k]``, the k-th key of ``concepts``."""
+    from ..engine.value_order import concept_words
+
+    names = list(concepts)
+    ids = tokens.reshape(-1).to(torch.int64)
+    hit = torch.zeros(ids.numel(), len(names), dtype=torch.bool, device=ids.device)
+    for k, name in enumerate(names):
+        hit[:, k] = torch.isin(ids, torch.as_tensor(list(concepts[name]), dtype=torch.int64, device=ids.device))
+    return concept_words(hit), names
+
+
+def stratified_examples(fc, vo, n_strata: int, per_stratum: int, fragment_len: int, features: slice = slice(None)):
+    """Quantile-binned example fragments of the features ``features`` (a contiguous slice, F of them): from the
+    value-ordered lists ``vo`` (``fc.by_value()``), per feature and stratum of its sorted activations (stratum
+    ``n_strata - 1`` holds the largest) ``per_stratum`` evenly spaced entries -- ``(frags int32, vals fp32) [G, F,
+    S, r]``, the fragment ``row // fragment_len`` of each picked row and its code, (-1, 0.0) in empty slots -- and
+    ``acts`` fp32 [G, F, S, r, L], the feature's activation record on each of those fragments
+    (``FeatureCodes.fragment_acts`` of the row-ordered ``fc``).  ``FragmentExamples`` shows a feature's top and
+    a random sample; this shows what is typical of its middle range."""
+    f0, f1, step = features.indices(fc.n)
+    if step != 1:
+        raise ValueError("features must be a contiguous slice")
+    f1 = max(f1, f0)
+    rows, vals = vo.strata(n_strata, per_stratum)
+    rows, vals = rows[:, f0:f1], vals[:, f0:f1]
+    L = int(fragment_len)
+    frags = torch.where(rows >= 0, torch.div(rows, L, rounding_mode="floor"), rows)
+    G, F, S, r = frags.shape
+    acts = fc.fragment_acts(frags.reshape(G, F, S * r).contiguous(), slice(f0, f1), L)
+    return frags, vals.contiguous(), acts.view(G, F, S, r, L)
 
 
 def get_dataset(learned_dict, lm: HookedLM, layer: int, layer_loc: str, n_feats: int, save_loc: str,
