@@ -548,8 +548,9 @@ int sc_fista_gram(const float* C, const void* Gm, const float* A0, const float* 
   const uint16_t* gm = reinterpret_cast<const uint16_t*>(Gm);
   uint16_t* ys = reinterpret_cast<uint16_t*>(Ysave);
   uint16_t* as = reinterpret_cast<uint16_t*>(Asave);
-  // 32-row workgroups when they still give >= 2 per CU (256 CUs); else 16 rows (rows = 16 forces it)
-  const bool two = (B % (2 * FR) == 0) && (long)G * (B / (2 * FR)) >= 512 && rows != 16;
+  // 32-row workgroups when they still give >= 2 per CU (256 CUs); else 16 rows (rows = 16 / 32 forces
+  // that height where it is instantiated for this (n, mode) -- tests, A/B; 0 = this heuristic)
+  const bool two = (B % (2 * FR) == 0) && rows != 16 && (rows == 32 || (long)G * (B / (2 * FR)) >= 512);
   const dim3 g2(G * (B / (2 * FR))), g1(G * (B / FR));
   // (NW, halves, ring depth) for 32-row, then 16-row workgroups: past n = 512 the fp32 iterates
   // need the column passes split, and the Gm ring shrinks to stay spill-free in 256 VGPRs
