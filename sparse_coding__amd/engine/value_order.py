@@ -37,7 +37,7 @@ _M32 = 0xFFFFFFFF
 
 def float_keys(val: torch.Tensor) -> torch.Tensor:
     """int64 keys in [0, 2^32) of fp32 values: ordered as unsigned integers they order the values, -0.0 before
-    +0.0, negative NaNs first and positive NaNs last (``co_order`` of ``csrc/coactivation.hip``)."""
+    +0.0, negative NaNs first and positive NaNs last (``order_key`` of ``csrc/common.h``)."""
     u = val.contiguous().view(torch.int32).to(torch.int64) & _M32
     return torch.where(u >= 0x80000000, u ^ _M32, u | 0x80000000)
 

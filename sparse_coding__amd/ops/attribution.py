@@ -7,12 +7,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .feature_codes import _lists
-from .interference import _buffer
-from .sparse_recon import _rows
-
-WAVES = (1, 2, 4)         # waves per block of the list walk
-INT32_MAX = 2 ** 31 - 1
+from ._args import INT32_MAX, WAVES, _buffer, _lists, _rows, check_waves, out_buffers  # noqa: F401 (WAVES is public)
 
 
 def residual_proj(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, D: torch.Tensor, x: torch.Tensor,
@@ -67,8 +62,7 @@ def attr_list_sums(col_ptr: torch.Tensor, frow: torch.Tensor, fval: torch.Tensor
     ``waves``: waves per block, 1, 2 or 4 -- the bits do not depend on it.  ``out``: the seven buffers to fill.
     One launch, one wave per list; nothing synchronises."""
     G, n, fcap, dev, frow_, fval_ = _lists(col_ptr, frow, fval)
-    if waves not in WAVES:
-        raise ValueError(f"waves must be one of {WAVES}, got {waves!r}")
+    waves = check_waves(waves)
     if row_ptr.dim() != 2 or row_ptr.dtype != torch.int64 or row_ptr.shape[0] != G or row_ptr.shape[1] < 1 \
             or not row_ptr.is_contiguous() or row_ptr.device != dev:
         raise ValueError(f"row_ptr must be contiguous int64 [{G}, N + 1] on the lists' device")
@@ -86,14 +80,9 @@ def attr_list_sums(col_ptr: torch.Tensor, frow: torch.Tensor, fval: torch.Tensor
         col, proj = row_ptr.new_zeros(G, 1, dtype=torch.int32), row_ptr.new_zeros(G, 1, dtype=torch.float32)
     spec = (("cnt", torch.int64), ("A", torch.float64), ("P1", torch.float64), ("C2", torch.float64),
             ("n_harm", torch.int64), ("min_delta", torch.float32), ("max_delta", torch.float32))
-    if out is None:
-        out = tuple(torch.empty(G, n, device=dev, dtype=dt) for _, dt in spec)
-    if len(out) != len(spec):
-        raise ValueError(f"out must hold the {len(spec)} buffers {[s[0] for s in spec]}")
-    for t, (name, dt) in zip(out, spec):
-        _buffer(f"out {name}", t, dt, (G, n), dev)
+    out = out_buffers([(name, dt, (G, n)) for name, dt in spec], out, dev)
     rc = _lib.lib().sc_attr_list_sums(_lib.ptr(col_ptr), _lib.ptr(frow_), _lib.ptr(fval_), _lib.ptr(row_ptr),
                                       _lib.ptr(col), _lib.ptr(proj), _lib.ptr(norm2), *(_lib.ptr(t) for t in out),
-                                      _lib.ptr(missing), G, n, fcap, N, N + 1, cap, int(waves), _lib.stream_handle())
+                                      _lib.ptr(missing), G, n, fcap, N, N + 1, cap, waves, _lib.stream_handle())
     _lib.check(rc, "sc_attr_list_sums")
-    return tuple(out)
+    return out

@@ -7,15 +7,13 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .feature_codes import _lists
-from .interference import _buffer
+from ._args import INT32_MAX, _buffer, _lists, out_buffers
 
 MAX_M = 32                # most partners per (source feature, target model)
 MAX_COLS = 16384          # widest target model: 64 KiB of int32 accumulators for one wave
 MAX_LDS = 65536           # bytes of accumulators per block
 MAX_WAVES = 4
 SCORES = ("pearson", "cosine", "jaccard")
-INT32_MAX = 2 ** 31 - 1
 
 
 def check_m(m) -> int:
@@ -134,13 +132,10 @@ def coactivation_topm(a_col_ptr: torch.Tensor, a_row: torch.Tensor, a_val: torch
     use_dot = mode != "jaccard"
     window, waves = geometry(n_b, use_dot, window, waves)
     shape = (Ga, Gb, n_a, m)
-    if out is None:
-        out = (torch.empty(shape, device=dev, dtype=torch.int32), torch.empty(shape, device=dev, dtype=torch.float32),
-               torch.empty(shape, device=dev, dtype=torch.int32), torch.empty(shape, device=dev, dtype=torch.float32))
-    partner, score, both, dot = out
-    for name, t, dt in (("partner", partner, torch.int32), ("score", score, torch.float32),
-                        ("both", both, torch.int32), ("dot", dot, torch.float32)):
-        _buffer(f"out {name}", t, dt, shape, dev)
+    if out is not None:
+        partner, score, both, dot = out  # (four buffers: any other length fails here, as an unpacking does)
+    partner, score, both, dot = out_buffers((("partner", torch.int32, shape), ("score", torch.float32, shape),
+                                             ("both", torch.int32, shape), ("dot", torch.float32, shape)), out, dev)
     if m == 0:
         return partner, score, both, dot
     if capb == 0:  # (no entry is stored: only empty rows pass the skip rule and no entry is read)

@@ -108,16 +108,10 @@ struct BiasArgs {
   int* step;                       // optional device step counter, advanced by loss_reduce
 };
 
-// Sums of a double over a wave (xor butterfly: every lane ends with the same bits) and over a 256-thread
-// block; `red` must hold >= 4 doubles of LDS.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
+// Sum of a double over a 256-thread block (per wave the xor butterfly 32 .. 1); `red` must hold >= 4 doubles
+// of LDS.
 __device__ __forceinline__ double block_sum_256_f64(double v, double* red) {
-  v = wave_sum_f64(v);
+  v = wave_sum_xor<false>(v);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) red[w] = v;
@@ -478,7 +472,7 @@ static int launch_tail(int d, int gbf16, int pol, long blocks, hipStream_t strea
     default: return 1;
   }
 #undef SC_TAIL
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 template <int NV, bool GBF>
@@ -519,7 +513,7 @@ int sc_adam_rows(int nset, float* const* p, const void* const* g, float* const* 
     default: return 1;
   }
 #undef SC_ADAM
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_shadow_rows(const float* p, void* shadow, float* norms, long rows, int d, int norm,
@@ -527,7 +521,7 @@ int sc_shadow_rows(const float* p, void* shadow, float* norms, long rows, int d,
   if (d % 4) return 1;
   hipLaunchKernelGGL(shadow_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, p,
                      reinterpret_cast<uint16_t*>(shadow), norms, rows, d, norm);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_bias_loss(int G, float* b, float* m, float* v, const float* colpart, int tm,
@@ -544,7 +538,7 @@ int sc_bias_loss(int G, float* b, float* m, float* v, const float* colpart, int 
   a.b1 = b1; a.b2 = b2; a.eps = eps; a.bc1 = bc1; a.bc2 = bc2; a.step = step;
   hipLaunchKernelGGL(loss_reduce_kernel, dim3(G), dim3(256), 0, stream, a);
   hipLaunchKernelGGL(bias_adam_kernel, dim3((n + 31) / 32, G), dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 // Fused step tail (see step_tail_kernel): row Adam over the sets + loss terms + bias Adam, the next

@@ -67,12 +67,12 @@ int sc_rowmatch_reduce(const void* part, int G, int Mp, int T, int M, float* val
     return 1;
   if (excl && (E < 1 || E > 8 || e0 < 0 || sexcl < (long)M * E)) return 1;
   const int row_blocks = (M + 15) / 16;
-  const long blocks = (long)G * row_blocks;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(rowmatch_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
+  unsigned blocks;
+  if (!sc_grid((long)G * row_blocks, 1, blocks)) return 1;
+  hipLaunchKernelGGL(rowmatch_reduce_kernel, dim3(blocks), dim3(256), 0, stream,
                      reinterpret_cast<const float2*>(part), T, Mp, M, val, idx, so, ldo, pass, excl, sexcl, E, e0,
                      nact_m, row_blocks);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 }  // extern "C"

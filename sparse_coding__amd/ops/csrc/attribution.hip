@@ -57,12 +57,11 @@ __global__ __launch_bounds__(64 * SR_ROWS) void residual_proj_kernel(
   const int g = (int)(id / n_rows);
   const long r = id - (long)g * n_rows;
   const long lo = row_ptr[(long)g * ldp + row0 + r], hi = row_ptr[(long)g * ldp + row0 + r + 1];
-  int lim = n;
-  if (nactive) lim = min(n, max(0, nactive[g]));
+  const int lim = live_limit(nactive, g, n);
   col += (long)g * cap;
   val += (long)g * cap;
   proj += (long)g * cap;
-  if (!sr_row_ok(lo, hi, cap, n, lim, col, lane)) {
+  if (!csr_row_ok(lo, hi, cap, n, lim, col, lane)) {
     if (lane == 0) {
       sse_row[id] = 0.f;
       atomicAdd(skipped + g, 1ull);
@@ -118,8 +117,7 @@ __global__ __launch_bounds__(64 * SR_ROWS) void residual_proj_kernel(
           float s = 0.f;
 #pragma unroll
           for (int i = 0; i < P; ++i) s = fmaf(res[i], sr_elem<P>(a[u], i), s);
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+          s = wave_sum_xor<true>(s);
           if (lane == i0 + u) myp = s;
         }
     }
@@ -128,38 +126,19 @@ __global__ __launch_bounds__(64 * SR_ROWS) void residual_proj_kernel(
   }
 }
 
-// Entry b + lane of a list that ends at hi: (row, code), or (-1, 0) past the end (row -1 is no valid row).
-__device__ __forceinline__ void at_load(const int* __restrict__ row, const float* __restrict__ val, long b, long hi,
-                                        int lane, int& r, float& c) {
-  r = -1;
-  c = 0.f;
-  if (b + lane < hi) {
-    r = row[b + lane];
-    c = val[b + lane];
-  }
-}
-
-template <class T>
-__device__ __forceinline__ T at_wave_sum(T v) {  // (a + b commutes: every lane ends with the same bits)
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64 * AT_WAVES) void attr_list_sums_kernel(
     const long* __restrict__ col_ptr, const int* __restrict__ frow, const float* __restrict__ fval, long fcap,
     long lists, int n, const long* __restrict__ row_ptr, long ldp, long N, const int* __restrict__ col,
     const float* __restrict__ proj, long cap, const float* __restrict__ norm2, int waves, long* __restrict__ cnt,
     double* __restrict__ A, double* __restrict__ P1, double* __restrict__ C2, long* __restrict__ n_harm,
     float* __restrict__ min_delta, float* __restrict__ max_delta, unsigned long long* __restrict__ missing) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (provably wave-uniform)
-  if (wave >= waves) return;
-  const long id = (long)blockIdx.x * waves + wave;  // (g, f) flattened
-  if (id >= lists) return;
-  const int g = (int)(id / n), f = (int)(id - (long)g * n);
-  const long* cp = col_ptr + (long)g * (n + 1);
-  const long lo = min(max(cp[f], 0l), fcap), hi = min(max(cp[f + 1], lo), fcap);  // 0 <= lo <= hi <= fcap
+  ListWalk w;
+  if (!list_walk(w, lists, waves)) return;
+  w.split(n);
+  const int lane = w.lane, g = w.g, f = w.f;
+  const long id = w.id;
+  long lo, hi;
+  list_bounds(col_ptr + (long)g * (n + 1), f, fcap, lo, hi);
   frow += (long)g * fcap;
   fval += (long)g * fcap;
   row_ptr += (long)g * ldp;
@@ -172,9 +151,9 @@ __global__ __launch_bounds__(64 * AT_WAVES) void attr_list_sums_kernel(
   float mn = INFINITY, mx = -INFINITY;
   int r0, r1;
   float c0, c1;
-  at_load(frow, fval, lo, hi, lane, r0, c0);
+  list_load(frow, fval, lo, hi, lane, r0, c0);
   for (long b = lo; b < hi; b += 64) {
-    at_load(frow, fval, b + 64, hi, lane, r1, c1);
+    list_load(frow, fval, b + 64, hi, lane, r1, c1);
     if (b + lane < hi) {
       bool found = false;
       float p = 0.f;
@@ -211,12 +190,12 @@ __global__ __launch_bounds__(64 * AT_WAVES) void attr_list_sums_kernel(
     r0 = r1;
     c0 = c1;
   }
-  a = at_wave_sum(a);
-  p1 = at_wave_sum(p1);
-  c2 = at_wave_sum(c2);
-  k = at_wave_sum(k);
-  harm = at_wave_sum(harm);
-  miss = at_wave_sum(miss);
+  a = wave_sum_xor<true>(a);
+  p1 = wave_sum_xor<true>(p1);
+  c2 = wave_sum_xor<true>(c2);
+  k = wave_sum_xor<true>(k);
+  harm = wave_sum_xor<true>(harm);
+  miss = wave_sum_xor<true>(miss);
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     mn = fminf(mn, __shfl_xor(mn, o, 64));
@@ -238,8 +217,6 @@ __global__ __launch_bounds__(64 * AT_WAVES) void attr_list_sums_kernel(
 
 using namespace scamd;
 
-static int at_launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 extern "C" {
 
 // Rows row0 .. row0 + n_rows - 1 of the CSR against D bf16 [G, n, d] and the rows x bf16, arguments as
@@ -257,7 +234,7 @@ int sc_residual_proj(const long* row_ptr, const int* col, const float* val, cons
                                          reinterpret_cast<const uint16_t*>(D), reinterpret_cast<const uint16_t*>(x),
                                          x_stride, nactive, G, n, proj, sse_row,
                                          reinterpret_cast<unsigned long long*>(skipped)))
-  return at_launched();
+  return sc_launched();
 }
 
 // The raw attribution sums of every (g, f) list of the feature-major codes (col_ptr int64 [G, n + 1], frow int32 /
@@ -275,12 +252,12 @@ int sc_attr_list_sums(const long* col_ptr, const int* frow, const float* fval, c
       waves < 1 || waves > AT_WAVES)
     return 1;
   const long lists = (long)G * n;
-  const long blocks = (lists + waves - 1) / waves;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(attr_list_sums_kernel, dim3((unsigned)blocks), dim3(64 * waves), 0, stream, col_ptr, frow, fval,
+  unsigned blocks;
+  if (!sc_grid(lists, waves, blocks)) return 1;
+  hipLaunchKernelGGL(attr_list_sums_kernel, dim3(blocks), dim3(64 * waves), 0, stream, col_ptr, frow, fval,
                      fcap, lists, n, row_ptr, ldp, N, col, proj, cap, norm2, waves, cnt, A, P1, C2, n_harm, min_delta,
                      max_delta, reinterpret_cast<unsigned long long*>(missing));
-  return at_launched();
+  return sc_launched();
 }
 
 }  // extern "C"

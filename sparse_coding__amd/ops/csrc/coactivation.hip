@@ -39,7 +39,7 @@
 // No floating-point atomics; every store sits behind its own bound.
 //
 // Known weak spot: a feature that fires on every row is one wave walking N rows in sequence.
-#include "common.h"
+#include "code_lists.h"
 
 namespace scamd {
 
@@ -49,35 +49,16 @@ constexpr int CO_MAX_COLS = 16384;     // widest target model
 constexpr int CO_PREFETCH = 8;         // target rows whose first 64 entries are in flight together
 constexpr int CO_MAX_M = 32;
 
-// LDS hand-off between the lanes of ONE wave (LDS operations of a wave complete in order).
-__device__ __forceinline__ void co_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The stored part [lo, hi) of list f of a model whose pointers are `cp` (0 <= lo <= hi <= cap whatever they hold).
-__device__ __forceinline__ void co_list(const long* __restrict__ cp, int f, long cap, long& lo, long& hi) {
-  lo = min(max(cp[f], 0l), cap);
-  hi = min(max(cp[f + 1], lo), cap);
-}
-
-__device__ __forceinline__ double co_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64 * CO_WAVES) void list_moments_kernel(
     const long* __restrict__ col_ptr, const float* __restrict__ val, long cap, long lists, int n,
     int* __restrict__ cnt, double* __restrict__ s1, double* __restrict__ s2) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (provably wave-uniform)
-  const long id = (long)blockIdx.x * CO_WAVES + wave;  // (g, f) flattened
-  if (id >= lists) return;
-  const int g = (int)(id / n), f = (int)(id - (long)g * n);
+  ListWalk w;
+  if (!list_walk(w, lists, CO_WAVES)) return;  // (every block has CO_WAVES waves; the wave index stays scalar)
+  w.split(n);
+  const int lane = w.lane, g = w.g;
+  const long id = w.id;
   long lo, hi;
-  co_list(col_ptr + (long)g * (n + 1), f, cap, lo, hi);
+  list_bounds(col_ptr + (long)g * (n + 1), w.f, cap, lo, hi);
   val += (long)g * cap;
   double a = 0.0, b = 0.0;
   for (long e = lo + lane; e < hi; e += 64) {
@@ -85,8 +66,8 @@ __global__ __launch_bounds__(64 * CO_WAVES) void list_moments_kernel(
     a = a + c;
     b = b + c * c;  // (c * c is exact in fp64: fused or not, the same bits)
   }
-  a = co_wave_sum_f64(a);
-  b = co_wave_sum_f64(b);
+  a = wave_sum_xor<true>(a);
+  b = wave_sum_xor<true>(b);
   if (lane == 0) {
     cnt[id] = (int)(hi - lo);
     s1[id] = a;
@@ -103,12 +84,6 @@ __device__ __forceinline__ float co_sub_mul(float a, float b, float c) {
   return __fsub_rn(a, p);
 }
 
-// Order-preserving map of a float's bits to unsigned integers.
-__device__ __forceinline__ uint32_t co_order(float s) {
-  const uint32_t u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 struct CoSlot {  // one slot of the sorted winners, one per lane (slots 0 .. m - 1); key 0: empty
   unsigned long long key;
   int both;
@@ -116,14 +91,11 @@ struct CoSlot {  // one slot of the sorted winners, one per lane (slots 0 .. m -
 };
 
 // Insert the wave-uniform candidate x (keys are distinct); one that does not beat slot K - 1 changes nothing.
-__device__ __forceinline__ void co_insert(CoSlot& cur, const CoSlot& x, int K, int lane) {
-  const unsigned long long kmask = K >= 64 ? ~0ull : (1ull << K) - 1ull;
-  const int pos = __popcll(__ballot(cur.key > x.key) & kmask);
-  CoSlot up;
-  up.key = __shfl_up(cur.key, 1, 64);
-  up.both = __shfl_up(cur.both, 1, 64);
-  up.dot = __shfl_up(cur.dot, 1, 64);
-  if (pos < K) cur = lane == pos ? x : lane > pos ? up : cur;
+__device__ __forceinline__ void insert_slot(CoSlot& cur, const CoSlot& x, int K, int lane) {
+  const int pos = insert_pos(cur.key > x.key, K);
+  insert_take(cur.key, x.key, pos, K, lane);
+  insert_take(cur.both, x.both, pos, K, lane);
+  insert_take(cur.dot, x.dot, pos, K, lane);
 }
 
 struct CoTarget {  // the CSR of target model h
@@ -215,17 +187,16 @@ __global__ __launch_bounds__(64 * CO_WAVES) void coact_topm_kernel(
     int min_both, int exclude_self, int W, int waves, int* __restrict__ partner, float* __restrict__ score,
     int* __restrict__ both, float* __restrict__ dot) {
   extern __shared__ int co_lds[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (provably wave-uniform)
-  if (wave >= waves) return;
-  const long id = (long)blockIdx.x * waves + wave;  // (g, f, h) flattened
-  if (id >= (long)Ga * n_a * Gb) return;
+  ListWalk lw;  // id: (g, f, h) flattened
+  if (!list_walk(lw, (long)Ga * n_a * Gb, waves)) return;
+  const int lane = lw.lane, wave = lw.wave;
+  const long id = lw.id;
   const int h = (int)(id % Gb), f = (int)((id / Gb) % n_a), g = (int)(id / ((long)Gb * n_a));
   int* ib = co_lds + (long)wave * (DOT ? 2 : 1) * W;  // both
   float* fd = reinterpret_cast<float*>(DOT ? ib + W : ib);  // dot (DOT: its own words; else the second walk's)
 
   long lo, hi;
-  co_list(a_col_ptr + (long)g * (n_a + 1), f, capa, lo, hi);
+  list_bounds(a_col_ptr + (long)g * (n_a + 1), f, capa, lo, hi);
   const int* arow = a_row + (long)g * capa;
   const float* aval = a_val + (long)g * capa;
   CoTarget t;
@@ -235,8 +206,7 @@ __global__ __launch_bounds__(64 * CO_WAVES) void coact_topm_kernel(
   t.N = N;
   t.cap = capb;
   t.n = n_b;
-  t.lim = n_b;
-  if (nactive_b) t.lim = min(n_b, max(0, nactive_b[h]));
+  t.lim = live_limit(nactive_b, h, n_b);
 
   const long af = (long)g * n_a + f;
   const float sha = shift_a[af], sca = scale_a[af];
@@ -257,9 +227,9 @@ __global__ __launch_bounds__(64 * CO_WAVES) void coact_topm_kernel(
         ib[o] = 0;
         if constexpr (DOT) fd[o] = 0.f;
       }
-      co_wave_sync();
+      wave_sync();
       co_walk<DOT ? 1 : 0>(lo, hi, arow, aval, t, fd, ib, c0, w, lane);
-      co_wave_sync();
+      wave_sync();
       for (int o0 = 0; o0 < w; o0 += 64) {
         const int o = o0 + lane, j = c0 + o;
         CoSlot x;
@@ -278,7 +248,7 @@ __global__ __launch_bounds__(64 * CO_WAVES) void coact_topm_kernel(
               s = __fdiv_rn((float)x.both, (float)(cna + cnt_b[j] - x.both));
             }
             s = __fadd_rn(s, 0.f);  // (-0.0 reads +0.0)
-            x.key = ((unsigned long long)co_order(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)j);
+            x.key = ((unsigned long long)order_key(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)j);
           }
         }
         const unsigned long long kth = __shfl(top.key, m - 1, 64);
@@ -290,10 +260,10 @@ __global__ __launch_bounds__(64 * CO_WAVES) void coact_topm_kernel(
           y.key = __shfl(x.key, i, 64);
           y.both = __shfl(x.both, i, 64);
           y.dot = __shfl(x.dot, i, 64);
-          co_insert(top, y, m, lane);
+          insert_slot(top, y, m, lane);
         }
       }
-      co_wave_sync();  // (the next window clears the words just read)
+      wave_sync();  // (the next window clears the words just read)
     }
     if constexpr (!DOT) {  // the dot of the winners: a second walk into the same words, window by window
       if (__ballot(lane < m && top.key != 0ull) != 0ull) {
@@ -301,11 +271,11 @@ __global__ __launch_bounds__(64 * CO_WAVES) void coact_topm_kernel(
         for (int c0 = 0; c0 < n_b; c0 += W) {
           const int w = min(W, n_b - c0);
           for (int o = lane; o < w; o += 64) fd[o] = 0.f;
-          co_wave_sync();
+          wave_sync();
           co_walk<2>(lo, hi, arow, aval, t, fd, ib, c0, w, lane);
-          co_wave_sync();
+          wave_sync();
           if (lane < m && top.key != 0ull && j >= c0 && j < c0 + w) top.dot = fd[j - c0];
-          co_wave_sync();
+          wave_sync();
         }
       }
     }
@@ -329,8 +299,6 @@ __global__ __launch_bounds__(64 * CO_WAVES) void coact_topm_kernel(
 
 using namespace scamd;
 
-static int co_launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 extern "C" {
 
 // Per (g, f) list of the feature-major codes (col_ptr int64 [G, n + 1], val fp32 [G, cap]): cnt int32 [G, n] its
@@ -339,11 +307,11 @@ int sc_list_moments(const long* col_ptr, const float* val, int* cnt, double* s1,
                     hipStream_t stream) {
   if (!col_ptr || !val || !cnt || !s1 || !s2 || G < 1 || n < 1 || cap < 0) return 1;
   const long lists = (long)G * n;
-  const long blocks = (lists + CO_WAVES - 1) / CO_WAVES;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(list_moments_kernel, dim3((unsigned)blocks), dim3(64 * CO_WAVES), 0, stream, col_ptr, val, cap,
+  unsigned blocks;
+  if (!sc_grid(lists, CO_WAVES, blocks)) return 1;
+  hipLaunchKernelGGL(list_moments_kernel, dim3(blocks), dim3(64 * CO_WAVES), 0, stream, col_ptr, val, cap,
                      lists, n, cnt, s1, s2);
-  return co_launched();
+  return sc_launched();
 }
 
 // The m best co-activation partners of every source list among the columns of every target model: partner int32,
@@ -368,9 +336,9 @@ int sc_coactivation_topm(const long* a_col_ptr, const int* a_row, const float* a
   const long bytes = (long)(use_dot ? 8 : 4) * window;
   if (window < 1 || waves < 1 || waves > CO_WAVES || bytes * waves > CO_MAX_LDS) return 1;
   const long work = (long)Ga * n_a * Gb;
-  const long blocks = (work + waves - 1) / waves;
-  if (blocks > 0x7fffffffL) return 1;
-  const dim3 grid((unsigned)blocks), block(64 * waves);
+  unsigned blocks;
+  if (!sc_grid(work, waves, blocks)) return 1;
+  const dim3 grid(blocks), block(64 * waves);
   const size_t lds = (size_t)(bytes * waves);
   if (use_dot)
     hipLaunchKernelGGL(coact_topm_kernel<true>, grid, block, lds, stream, a_col_ptr, a_row, a_val, capa, Ga, n_a,
@@ -380,7 +348,7 @@ int sc_coactivation_topm(const long* a_col_ptr, const int* a_row, const float* a
     hipLaunchKernelGGL(coact_topm_kernel<false>, grid, block, lds, stream, a_col_ptr, a_row, a_val, capa, Ga, n_a,
                        b_row_ptr, ldp, N, b_col, b_val, capb, Gb, n_b, nactive_b, shift_a, scale_a, cnt_a, shift_b,
                        scale_b, cnt_b, m, min_both, exclude_self, window, waves, partner, score, both, dot);
-  return co_launched();
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -31,11 +31,17 @@ enum { ST_PLAIN = 0, ST_NT = 2, ST_SC1 = 16, ST_NT_SC1 = 18 };
 // 32-bit, so the host keeps write-through off for any output that spans more (ops/store_policy.py).
 // `base` must be wave-uniform; the readfirstlanes make that provable (no waterfall loops).
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
+
+// A 64-bit value every lane holds, handed on as a provably wave-uniform one (two readfirstlanes).
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
 __device__ __forceinline__ rsrc_t store_rsrc(const void* base) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  const uint64_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-  const uint64_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((hi << 32) | lo), 0, 0x7FFFFFFF, 0x00020000);
+  const uint64_t a = uniform_u64(reinterpret_cast<uint64_t>(base));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(a), 0, 0x7FFFFFFF, 0x00020000);
 }
 
 // One whole 16-byte or 8-byte store of `v` at base + off under policy POL.  The plain and `nt` forms
@@ -106,6 +112,34 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// Wave-wide sum by the xor butterfly: every lane ends with the same bits.  ASCENDING joins the lanes at
+// offsets 1, 2, 4, 8, 16, 32, the other order at 32, 16, 8, 4, 2, 1.  The two orders round differently
+// in fp32 and fp64, and each caller's order is a contract that its oracle emulates bit for bit: both
+// stay, and a caller keeps the one it has.  (Integers: either order, the same bits.)
+template <bool ASCENDING, class T>
+__device__ __forceinline__ T wave_sum_xor(T v) {
+  if constexpr (ASCENDING) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
+  } else {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  }
+  return v;
+}
+
+// LDS hand-off between the lanes of ONE wave (LDS operations of a wave complete in order).
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Order-preserving map of an fp32 bit pattern to unsigned integers (larger float -> larger key): a total
+// order on all bit patterns, so -0.0 sorts before +0.0 and every NaN has its place.
+__device__ __forceinline__ uint32_t order_key(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ uint32_t order_key(float f) { return order_key(__float_as_uint(f)); }
 
 // Block-wide sum for a 256-thread block; `red` must hold >= 4 floats of LDS.
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
@@ -188,3 +222,14 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 }
 
 }  // namespace scamd
+
+// ------------------------------------------------------------------ host side of every entry point
+// What an entry point returns after its launches: 0 when they were accepted, 3 otherwise.
+static inline int sc_launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
+
+// blocks = the blocks of `per` items that cover `work`; false when a 1-D grid cannot hold them.
+static inline bool sc_grid(long work, long per, unsigned& blocks) {
+  const long b = (work + per - 1) / per;
+  blocks = (unsigned)b;
+  return b <= 0x7fffffffL;
+}

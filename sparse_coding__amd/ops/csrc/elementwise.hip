@@ -302,7 +302,7 @@ int sc_center_rows(const void* x, const float* c, void* out, int G, int B, int d
   const long total = (long)G * B * d / 4;
   hipLaunchKernelGGL(center_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<const uint16_t*>(x), c, reinterpret_cast<uint16_t*>(out), G, B, d);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_lista_fwd(const float* y, const float* a, const float* xs, const float* theta, const float* m, float* xo,
@@ -313,7 +313,7 @@ int sc_lista_fwd(const float* y, const float* a, const float* xs, const float* t
                      reinterpret_cast<const float4*>(y), reinterpret_cast<const float4*>(a),
                      reinterpret_cast<const float4*>(xs), theta, m, reinterpret_cast<float4*>(xo),
                      reinterpret_cast<float4*>(yo), nullptr, nullptr, nullptr, B, n, total4);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 // The explicit step's forward: also r (may be a itself), the bf16 y', and |y'| block sums
@@ -327,7 +327,7 @@ int sc_lista_fwd2(const float* y, const float* a, const float* xs, const float* 
                      reinterpret_cast<const float4*>(xs), theta, m, reinterpret_cast<float4*>(xo),
                      reinterpret_cast<float4*>(yo), reinterpret_cast<float4*>(r_out),
                      reinterpret_cast<ushort4*>(yob), absp, B, n, total4);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 // gth_part: [G][B / rb][n], gm_part: [G][B / rb][n / 256]
@@ -337,7 +337,7 @@ int sc_lista_bwd(const float* gy, const float* gx, const float* y, const float* 
   if (n % 256 || rb < 4 || rb % 4 || B % rb || G < 1) return 1;
   hipLaunchKernelGGL(lista_bwd_kernel, dim3(n / 256, B / rb, G), dim3(256), 0, stream, gy, nullptr, gx, y, a, xs,
                      theta, m, nullptr, gr, nullptr, 1.f, gxs, nullptr, gth_part, gm_part, B, n, rb);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_lista_bwd2(const float* gy, const float* gy2, const float* gx, const float* y, const float* a, const float* xs,
@@ -347,7 +347,7 @@ int sc_lista_bwd2(const float* gy, const float* gy2, const float* gx, const floa
   hipLaunchKernelGGL(lista_bwd_kernel, dim3(n / 256, B / rb, G), dim3(256), 0, stream, gy, gy2, gx, y, a, xs,
                      theta, m, l1c, gr, reinterpret_cast<uint16_t*>(grb), gsign, gxs, reinterpret_cast<uint16_t*>(ub),
                      gth_part, gm_part, B, n, rb);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_res_fwd(const float* u, const float* c, const float* th, float* cout, void* hb, float* absp, int fin, int G,
@@ -357,7 +357,7 @@ int sc_res_fwd(const float* u, const float* c, const float* th, float* cout, voi
   hipLaunchKernelGGL(res_fwd_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<const float4*>(u), reinterpret_cast<const float4*>(c), th,
                      reinterpret_cast<float4*>(cout), reinterpret_cast<ushort4*>(hb), absp, fin, B, n, total4);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_res_bwd(const float* gin, const float* gadd, const float* pre, const float* th, const float* l1c, float* out,
@@ -365,7 +365,7 @@ int sc_res_bwd(const float* gin, const float* gadd, const float* pre, const floa
   if (n % 256 || rb < 4 || rb % 4 || B % rb || G < 1) return 1;
   hipLaunchKernelGGL(res_bwd_kernel, dim3(n / 256, B / rb, G), dim3(256), 0, stream, gin, gadd, pre, th, l1c, out,
                      reinterpret_cast<uint16_t*>(outb), cpart, B, n, rb);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_gather_rows(const void* buf, const long* idx, void* out, long rows, long row_bytes, hipStream_t stream) {
@@ -374,7 +374,7 @@ int sc_gather_rows(const void* buf, const long* idx, void* out, long rows, long 
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
                      reinterpret_cast<const u32x4_t*>(buf), idx, reinterpret_cast<u32x4_t*>(out), rows,
                      (int)(row_bytes / 16));
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_gather_rows_perm(const void* buf, long nbuf, const long* perm, long nperm, const int* step, const int* ep0,
@@ -388,7 +388,7 @@ int sc_gather_rows_perm(const void* buf, long nbuf, const long* perm, long nperm
   hipLaunchKernelGGL(gather_rows_perm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
                      reinterpret_cast<const u32x4_t*>(buf), nbuf, perm, nperm, step, ep0,
                      reinterpret_cast<u32x4_t*>(out), rows, (int)(row_bytes / 16), stride, offset, inner, ostride);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_gather_rows_blocks(const void* buf, long nbuf, const long* perm, long nperm, long base, long stride,
@@ -399,7 +399,7 @@ int sc_gather_rows_blocks(const void* buf, long nbuf, const long* perm, long npe
   hipLaunchKernelGGL(gather_rows_blocks_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
                      reinterpret_cast<const u32x4_t*>(buf), nbuf, perm, nperm, base, stride, inner,
                      reinterpret_cast<u32x4_t*>(out), rows, (int)(row_bytes / 16));
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 }  // extern "C"

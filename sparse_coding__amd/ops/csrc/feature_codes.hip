@@ -40,35 +40,13 @@
 //                      fragment frags[g, f, k], 0 where it does not fire, all zeros for a slot outside
 //                      [0, n_frags).  A wave-uniform binary search finds the fragment's first entry, a per-lane
 //                      search over the next <= L entries the row of each output.  Every element is written.
-#include "common.h"
+#include "code_lists.h"
 
 namespace scamd {
 
 constexpr int FC_WAVES = 4;            // waves per block, all kernels
 constexpr int FC_MAX_LDS_BINS = 16384;  // 64 KiB of int32 bins: the largest LDS histogram a launch may ask for
 constexpr int FC_MAX_SEG_SHIFT = 13;    // segments of at most 8192 rows (2 KiB of bitmap and prefix per wave)
-
-// LDS hand-off between the lanes of ONE wave (LDS operations of a wave complete in order).
-__device__ __forceinline__ void fc_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The skip rule (wave-uniform result).  `col` is the model's column array.
-__device__ __forceinline__ bool fc_row_ok(long lo, long hi, long cap, int n, int lim, const int* __restrict__ col,
-                                          int lane) {
-  bool ok = lo >= 0 && hi >= lo && hi <= cap && hi - lo <= (long)n;
-  if (ok) {
-    bool bad = false;
-    for (long e = lo + lane; e < hi; e += 64) {
-      const int j = col[e];
-      bad |= (j < 0) | (j >= lim);
-    }
-    ok = __ballot(bad) == 0ull;
-  }
-  return ok;
-}
 
 struct FcWalk {  // what a block of the two row walks works on
   int g, s;
@@ -83,8 +61,7 @@ __device__ __forceinline__ FcWalk fc_walk(long N, int n, int seg_shift, int rpb,
   w.s = blockIdx.x / bps;
   w.r0 = ((long)w.s << seg_shift) + (long)(blockIdx.x % bps) * rpb;
   w.r1 = min(w.r0 + rpb, N);
-  w.lim = n;
-  if (nactive) w.lim = min(n, max(0, nactive[w.g]));
+  w.lim = live_limit(nactive, w.g, n);
   return w;
 }
 
@@ -105,7 +82,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fc_count_kernel(
   int* gc = cnt + ((long)w.g * S + w.s) * n;
   for (long r = w.r0 + wave; r < w.r1; r += FC_WAVES) {
     const long lo = row_ptr[r], hi = row_ptr[r + 1];
-    if (!fc_row_ok(lo, hi, cap, n, w.lim, col, lane)) {
+    if (!csr_row_ok(lo, hi, cap, n, w.lim, col, lane)) {
       if (lane == 0) atomicAdd(skipped + w.g, 1ull);
       continue;
     }
@@ -147,7 +124,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fc_scatter_kernel(
     __syncthreads();
     for (long r = w.r0 + wave; r < w.r1; r += FC_WAVES) {
       const long lo = row_ptr[r], hi = row_ptr[r + 1];
-      const bool ok = fc_row_ok(lo, hi, cap, n, w.lim, col, lane);
+      const bool ok = csr_row_ok(lo, hi, cap, n, w.lim, col, lane);
       if (lane == 0) okf[r - w.r0] = ok;
       if (!ok) continue;
       for (long e = lo + lane; e < hi; e += 64) {
@@ -169,7 +146,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fc_scatter_kernel(
       if (!okf[r - w.r0]) continue;
       if (!(lo >= 0 && hi >= lo && hi <= cap)) continue;  // (the verdict covered these pointers)
     } else {
-      if (!fc_row_ok(lo, hi, cap, n, w.lim, col, lane)) continue;
+      if (!csr_row_ok(lo, hi, cap, n, w.lim, col, lane)) continue;
     }
     for (long e = lo + lane; e < hi; e += 64) {
       const int j = col[e];
@@ -193,9 +170,10 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fc_order_kernel(
     int* __restrict__ orow, float* __restrict__ oval, long ocap,
     long lists, int n, int S, int seg_shift) {
   extern __shared__ uint32_t fc_bits[];  // per wave: W words of bitmap, W words of exclusive prefix
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long id = (long)blockIdx.x * FC_WAVES + wave;  // (g, s, f) flattened, as cnt and base
-  if (id >= lists) return;
+  ListWalk w;  // id: (g, s, f) flattened, as cnt and base
+  if (!list_walk<FC_WAVES>(w, lists)) return;
+  const int lane = w.lane, wave = w.wave;
+  const long id = w.id;
   long len = cnt[id];
   const long start = base[id];
   if (len <= 0 || start < 0 || start >= tcap) return;
@@ -209,12 +187,12 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fc_order_kernel(
   orow += (long)g * ocap;
   oval += (long)g * ocap;
   for (int q = lane; q < W; q += 64) bm[q] = 0u;
-  fc_wave_sync();
+  wave_sync();
   for (long i = lane; i < len; i += 64) {
     const long o = (long)(int)tmp[i][0] - seg0;
     if (o >= 0 && o < seg) atomicOr(&bm[o >> 5], 1u << (o & 31));
   }
-  fc_wave_sync();
+  wave_sync();
   int carry = 0;
   for (int q0 = 0; q0 < W; q0 += 64) {
     const int q = q0 + lane;
@@ -228,7 +206,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fc_order_kernel(
     if (q < W) pre[q] = (uint32_t)(carry + incl - c);
     carry += __shfl(incl, 63, 64);
   }
-  fc_wave_sync();
+  wave_sync();
   for (long i = lane; i < len; i += 64) {
     const u32x2_t rv = tmp[i];
     const int r = (int)rv[0];
@@ -256,12 +234,8 @@ __device__ __forceinline__ uint32_t fc_mix32(uint32_t x) {
 // Insert the wave-uniform key x into the sorted list held one slot per lane (slots 0 .. K-1; DESC: largest
 // first).  Keys are distinct.  A key that does not beat slot K-1 changes nothing.
 template <bool DESC>
-__device__ __forceinline__ void fc_insert(unsigned long long& cur, unsigned long long x, int K, int lane) {
-  const unsigned long long kmask = (1ull << K) - 1ull;  // (K <= 32)
-  const bool before = DESC ? cur > x : cur < x;
-  const int pos = __popcll(__ballot(before) & kmask);
-  const unsigned long long up = __shfl_up(cur, 1, 64);
-  if (pos < K) cur = lane == pos ? x : lane > pos ? up : cur;
+__device__ __forceinline__ void insert_key(unsigned long long& cur, unsigned long long x, int K, int lane) {
+  insert_take(cur, x, insert_pos(DESC ? cur > x : cur < x, K), K, lane);
 }
 
 __device__ __forceinline__ unsigned long long fc_top_key(float v, uint32_t frag) {
@@ -272,22 +246,17 @@ __device__ __forceinline__ unsigned long long fc_rnd_key(uint32_t h0, uint32_t f
   return ((unsigned long long)fc_mix32(h0 ^ frag) << 32) | (unsigned long long)frag;
 }
 
-// The stored part [lo, hi) of list f of a model whose pointers are `cp` (0 <= lo <= hi <= cap whatever they hold).
-__device__ __forceinline__ void fc_list(const long* __restrict__ cp, int f, long cap, long& lo, long& hi) {
-  lo = min(max(cp[f], 0l), cap);
-  hi = min(max(cp[f + 1], lo), cap);
-}
-
 __global__ __launch_bounds__(64 * FC_WAVES) void fragment_examples_kernel(
     const long* __restrict__ col_ptr, const int* __restrict__ row, const float* __restrict__ val, long cap, int G,
     int n, uint32_t L, int Kt, int Kr, uint32_t seed, long* __restrict__ n_frags, int* __restrict__ top_frag,
     float* __restrict__ top_max, int* __restrict__ rand_frag) {
-  const int lane = threadIdx.x & 63;
-  const long id = (long)blockIdx.x * FC_WAVES + (threadIdx.x >> 6);  // (g, f) flattened
-  if (id >= (long)G * n) return;
-  const int g = (int)(id / n), f = (int)(id - (long)g * n);
+  ListWalk w;
+  if (!list_walk<FC_WAVES>(w, (long)G * n)) return;
+  w.split(n);
+  const int lane = w.lane, g = w.g;
+  const long id = w.id;
   long lo, hi;
-  fc_list(col_ptr + (long)g * (n + 1), f, cap, lo, hi);
+  list_bounds(col_ptr + (long)g * (n + 1), w.f, cap, lo, hi);
   row += (long)g * cap;
   val += (long)g * cap;
   const uint32_t h0 = fc_mix32(seed + 0x9E3779B9u * (uint32_t)(id + 1));
@@ -298,8 +267,8 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fragment_examples_kernel(
   float omax = 0.f;
   auto single = [&](uint32_t fr, float v) {  // one closed run, wave-uniform
     ++nfr;
-    if (Kt) fc_insert<true>(top, fc_top_key(v, fr), Kt, lane);
-    if (Kr) fc_insert<false>(rnd, fc_rnd_key(h0, fr), Kr, lane);
+    if (Kt) insert_key<true>(top, fc_top_key(v, fr), Kt, lane);
+    if (Kr) insert_key<false>(rnd, fc_rnd_key(h0, fr), Kr, lane);
   };
   for (long b = lo; b < hi; b += 64) {
     const int cnt = (int)min(64l, hi - b);
@@ -331,7 +300,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fragment_examples_kernel(
       while (m) {
         const int i = __ffsll((long long)m) - 1;
         m &= m - 1ull;
-        fc_insert<true>(top, __shfl(k, i, 64), Kt, lane);
+        insert_key<true>(top, __shfl(k, i, 64), Kt, lane);
       }
     }
     if (Kr) {
@@ -341,7 +310,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fragment_examples_kernel(
       while (m) {
         const int i = __ffsll((long long)m) - 1;
         m &= m - 1ull;
-        fc_insert<false>(rnd, __shfl(k, i, 64), Kr, lane);
+        insert_key<false>(rnd, __shfl(k, i, 64), Kr, lane);
       }
     }
     open = true;
@@ -360,9 +329,10 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fragment_examples_kernel(
 __global__ __launch_bounds__(64 * FC_WAVES) void fragment_acts_kernel(
     const long* __restrict__ col_ptr, const int* __restrict__ row, const float* __restrict__ val, long cap, int n,
     int f0, int nf, int K, int L, long nfrag, long slots, const int* __restrict__ frags, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const long id = (long)blockIdx.x * FC_WAVES + (threadIdx.x >> 6);  // (g, f - f0, k) flattened
-  if (id >= slots) return;
+  ListWalk w;  // id: (g, f - f0, k) flattened
+  if (!list_walk<FC_WAVES>(w, slots)) return;
+  const int lane = w.lane;
+  const long id = w.id;
   const int g = (int)(id / ((long)nf * K)), f = f0 + (int)((id / K) % nf);
   float* o = out + id * L;
   const long fr = frags[id];
@@ -371,7 +341,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fragment_acts_kernel(
     return;
   }
   long lo, hi;
-  fc_list(col_ptr + (long)g * (n + 1), f, cap, lo, hi);
+  list_bounds(col_ptr + (long)g * (n + 1), f, cap, lo, hi);
   row += (long)g * cap;
   val += (long)g * cap;
   const long r0 = fr * L;
@@ -397,8 +367,6 @@ __global__ __launch_bounds__(64 * FC_WAVES) void fragment_acts_kernel(
 }  // namespace scamd
 
 using namespace scamd;
-
-static int fc_launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
 
 static bool fc_bad_walk(const void* row_ptr, const void* col, int G, long N, int n, long ldp, long cap, int seg_shift,
                         int S, int rpb, int use_lds) {
@@ -430,7 +398,7 @@ int sc_feature_count(const long* row_ptr, const int* col, const int* nactive, in
   else
     hipLaunchKernelGGL(fc_count_kernel<false>, grid, dim3(64 * FC_WAVES), 0, stream, row_ptr, ldp, N, col, cap, nactive,
                        n, seg_shift, S, rpb, bps, cnt, reinterpret_cast<unsigned long long*>(skipped));
-  return fc_launched();
+  return sc_launched();
 }
 
 // The same walk: every entry of a valid row goes to tmp[g, base[g, s, f] + its reserved position], behind
@@ -451,7 +419,7 @@ int sc_feature_scatter(const long* row_ptr, const int* col, const float* val, co
   else
     hipLaunchKernelGGL(fc_scatter_kernel<false>, grid, dim3(64 * FC_WAVES), 0, stream, row_ptr, ldp, N, col, val, cap,
                        nactive, n, seg_shift, S, rpb, bps, base, cur, reinterpret_cast<u32x2_t*>(tmp), tcap);
-  return fc_launched();
+  return sc_launched();
 }
 
 // Every sub-list (g, s, f) of the temporary buffer, rows ascending, into (orow, oval) [G, ocap] behind position < ocap.
@@ -461,12 +429,12 @@ int sc_feature_order(const int* cnt, const long* base, const void* tmp, int* oro
       seg_shift > FC_MAX_SEG_SHIFT || tcap < 0 || ocap < 0)
     return 1;
   const long lists = (long)G * S * n;
-  const long blocks = (lists + FC_WAVES - 1) / FC_WAVES;
-  if (blocks > 0x7fffffffL) return 1;
+  unsigned blocks;
+  if (!sc_grid(lists, FC_WAVES, blocks)) return 1;
   const size_t lds = (size_t)FC_WAVES * 2 * ((1 << seg_shift) >> 5) * sizeof(uint32_t);
-  hipLaunchKernelGGL(fc_order_kernel, dim3((unsigned)blocks), dim3(64 * FC_WAVES), lds, stream, cnt, base,
+  hipLaunchKernelGGL(fc_order_kernel, dim3(blocks), dim3(64 * FC_WAVES), lds, stream, cnt, base,
                      reinterpret_cast<const u32x2_t*>(tmp), tcap, orow, oval, ocap, lists, n, S, seg_shift);
-  return fc_launched();
+  return sc_launched();
 }
 
 // Per (g, f) list of the feature-major codes (col_ptr int64 [G, n + 1], row int32 / val fp32 [G, cap]): n_frags
@@ -476,11 +444,11 @@ int sc_fragment_examples(const long* col_ptr, const int* row, const float* val, 
                          unsigned seed, hipStream_t stream) {
   if (!col_ptr || !row || !val || !n_frags || G < 1 || n < 1 || cap < 0 || L < 1 || L > 0x7fffffffL) return 1;
   if (Kt < 0 || Kt > 32 || Kr < 0 || Kr > 32 || (Kt && (!top_frag || !top_max)) || (Kr && !rand_frag)) return 1;
-  const long blocks = ((long)G * n + FC_WAVES - 1) / FC_WAVES;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(fragment_examples_kernel, dim3((unsigned)blocks), dim3(64 * FC_WAVES), 0, stream, col_ptr, row,
+  unsigned blocks;
+  if (!sc_grid((long)G * n, FC_WAVES, blocks)) return 1;
+  hipLaunchKernelGGL(fragment_examples_kernel, dim3(blocks), dim3(64 * FC_WAVES), 0, stream, col_ptr, row,
                      val, cap, G, n, (uint32_t)L, Kt, Kr, (uint32_t)seed, n_frags, top_frag, top_max, rand_frag);
-  return fc_launched();
+  return sc_launched();
 }
 
 // out fp32 [G, nf, K, L]: the codes of features f0 .. f0 + nf - 1 on the rows of the fragments frags int32 [G, nf, K]
@@ -491,11 +459,11 @@ int sc_fragment_acts(const long* col_ptr, const int* row, const float* val, cons
       (long)f0 + nf > n || n_frag < 0 || n_frag > 0x7fffffffL / L)
     return 1;
   const long slots = (long)G * nf * K;
-  const long blocks = (slots + FC_WAVES - 1) / FC_WAVES;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(fragment_acts_kernel, dim3((unsigned)blocks), dim3(64 * FC_WAVES), 0, stream, col_ptr, row, val,
+  unsigned blocks;
+  if (!sc_grid(slots, FC_WAVES, blocks)) return 1;
+  hipLaunchKernelGGL(fragment_acts_kernel, dim3(blocks), dim3(64 * FC_WAVES), 0, stream, col_ptr, row, val,
                      cap, n, f0, nf, K, L, n_frag, slots, frags, out);
-  return fc_launched();
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -215,11 +215,11 @@ extern "C" {
 // out fp32 [G, S, 6, n]; S slabs of B / S rows each (a multiple of 16).
 int sc_col_moments(const void* c, float* out, int G, int B, int n, int S, hipStream_t stream) {
   if (!c || !out || G < 1 || B < 128 || B % 128 || n < 128 || n % 128 || S < 1 || B % S || (B / S) % 16) return 1;
-  const long blocks = (long)G * S * (n / 128);
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(col_moments_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
+  unsigned blocks;
+  if (!sc_grid((long)G * S * (n / 128), 1, blocks)) return 1;
+  hipLaunchKernelGGL(col_moments_kernel, dim3(blocks), dim3(256), 0, stream,
                      reinterpret_cast<const uint16_t*>(c), out, B, n, B / S);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 // top_vals fp32 [G, n, K], top_rows int64 [G, n, K], 1 <= K <= 32; the batch's rows are row0 .. row0 + B - 1.
@@ -228,11 +228,11 @@ int sc_col_topk(const void* c, float* top_vals, long* top_rows, int G, int B, in
   if (!c || !top_vals || !top_rows || G < 1 || B < 128 || B % 128 || n < 128 || n % 128 || K < 1 || K > TK_MAXK ||
       row0 < 0)
     return 1;
-  const long blocks = (long)G * (n / TK_COLS);
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(col_topk_kernel, dim3((unsigned)blocks), dim3(TK_THREADS), 0, stream,
+  unsigned blocks;
+  if (!sc_grid((long)G * (n / TK_COLS), 1, blocks)) return 1;
+  hipLaunchKernelGGL(col_topk_kernel, dim3(blocks), dim3(TK_THREADS), 0, stream,
                      reinterpret_cast<const uint16_t*>(c), top_vals, top_rows, B, n, K, row0);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 }  // extern "C"

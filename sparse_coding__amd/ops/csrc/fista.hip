@@ -509,7 +509,7 @@ static int launch_direct(const FistaArgs& a, int G, hipStream_t stream, int rows
     hipFuncSetAttribute((const void*)fista_kernel<DWV, NWV, RTV, MV>,                                     \
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);                            \
     hipLaunchKernelGGL((fista_kernel<DWV, NWV, RTV, MV>), dim3(G * (B / (RTV * FR))), dim3(FNT), LDS, stream, a); \
-    return hipGetLastError() == hipSuccess ? 0 : 3;                                                       \
+    return sc_launched();                                                                                 \
   }
 #define SC_F(DWV, NWV)                                                                                    \
   if (DW == DWV && NW == NWV) {                                                                           \
@@ -560,7 +560,7 @@ int sc_fista_gram(const float* C, const void* Gm, const float* A0, const float* 
                                 mom, A, B, T, ys, as, Vsum, qs, epart);                                               \
     else hipLaunchKernelGGL((fista_gram_kernel<NWV, 1, H1, PF1, MV>), g1, dim3(FNT), 0, stream, C, gm, A0, eta, lam, \
                             mom, A, B, T, ys, as, Vsum, qs, epart);                                                   \
-    return hipGetLastError() == hipSuccess ? 0 : 3;                                                        \
+    return sc_launched();                                                                                  \
   }
   // (NW, halves, ring depth) of the 32-row and 16-row solve, then of the slab-saving solve and
   // the adjoint (its Vbar sum needs registers: more halves, shallower rings; past n = 512 the
@@ -575,7 +575,7 @@ int sc_fista_gram(const float* C, const void* Gm, const float* A0, const float* 
 #define SC_G1(NWV, H1, PF1, MV)                                                                            \
   hipLaunchKernelGGL((fista_gram_kernel<NWV, 1, H1, PF1, MV>), g1, dim3(FNT), 0, stream, C, gm, A0, eta, lam, mom, A, B, \
                      T, ys, as, Vsum, qs, epart);                                                                     \
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
   SC_G(2, 1, 4, 1, 4, SC_GM(2, 1, 4, 1, 4, 1), SC_GM(2, 1, 4, 1, 4, 2))
   SC_G(4, 1, 4, 1, 8, SC_GM(4, 1, 4, 1, 4, 1), SC_GM(4, 4, 1, 1, 2, 2))
   SC_G(6, 2, 2, 2, 4, SC_GM(6, 2, 2, 2, 4, 1), SC_G1(6, 3, 1, 2))

@@ -151,7 +151,7 @@ int sc_hessian_ema(const float* A, float* H, int G, int B, int n, float history,
   if (n % 64 || G < 1 || B < 1 || history <= 0.f) return 1;
   hipLaunchKernelGGL(hessian_ema_kernel, dim3(n / 64, G), dim3(256), 0, stream, A, H, B, n,
                      (history - 1.f) / history, 1.f / (history * (float)B));
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 // D [G, n, d] += dBt / (H + lowest) (per atom), optional clamp, renormalise rows (mode 1) or
@@ -169,7 +169,7 @@ int sc_basis_apply(float* D, const float* dBt, const float* H, void* Db, int G, 
     hipLaunchKernelGGL(basis_apply_cols_kernel, dim3(d / 64, G), dim3(256), 0, stream, D, dBt, H, db, n, d, lowest,
                        nonneg);
   }
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_fista_adjoint(const float* T2, float* Vbar, const float* Ynext, float* Ycur, const void* Aslab, void* Vslab,
@@ -180,7 +180,7 @@ int sc_fista_adjoint(const float* T2, float* Vbar, const float* Ynext, float* Yc
   hipLaunchKernelGGL(fista_adjoint_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, T2, Vbar,
                      Ynext, Ycur, reinterpret_cast<const uint16_t*>(Aslab), reinterpret_cast<uint16_t*>(Vslab), cbar,
                      eta, m_prev, m_t, B, n, T, t, total);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_fista_adjoint_init(const float* T2, float* Vbar, const void* Aslab, void* Vslab, int G, int B, int n, int T,
@@ -190,7 +190,7 @@ int sc_fista_adjoint_init(const float* T2, float* Vbar, const void* Aslab, void*
   hipLaunchKernelGGL(fista_adjoint_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, T2,
                      Vbar, reinterpret_cast<const uint16_t*>(Aslab), reinterpret_cast<uint16_t*>(Vslab), B, n, T,
                      total);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -36,7 +36,7 @@
 // to skipped[g] -- unless 0 <= row_ptr[g, r] <= row_ptr[g, r + 1] <= cap, L <= n, and every column is in
 // [0, lim), lim = n or min(n, nactive[g]).  All columns are checked before the first gather, and every
 // entry_cap store is behind pos < cap.
-#include "common.h"
+#include "code_lists.h"
 
 namespace scamd {
 
@@ -86,21 +86,11 @@ __global__ __launch_bounds__(64 * IC_ROWS) __attribute__((amdgpu_waves_per_eu(3)
   const int g = (int)(id / n_rows);
   const long r = id - (long)g * n_rows;
   const long lo = row_ptr[(long)g * ldp + row0 + r], hi = row_ptr[(long)g * ldp + row0 + r + 1];
-  int lim = n;
-  if (nactive) lim = min(n, max(0, nactive[g]));
+  const int lim = live_limit(nactive, g, n);
   col += (long)g * cap;
   val += (long)g * cap;
   // ---- validate before anything is gathered (all tests wave-uniform)
-  bool ok = lo >= 0 && hi >= lo && hi <= cap && hi - lo <= (long)n;
-  if (ok) {
-    bool bad = false;
-    for (long e = lo + lane; e < hi; e += 64) {
-      const int j = col[e];
-      bad |= (j < 0) | (j >= lim);
-    }
-    ok = __ballot(bad) == 0ull;
-  }
-  if (!ok) {
+  if (!csr_row_ok(lo, hi, cap, n, lim, col, lane)) {
     if (lane == 0) atomicAdd(skipped + g, 1ull);
     return;
   }
@@ -252,19 +242,17 @@ __global__ __launch_bounds__(64 * IC_ROWS) __attribute__((amdgpu_waves_per_eu(3)
 
 using namespace scamd;
 
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 extern "C" {
 
 // D bf16 [G, n, d] -> norm2 fp32 [G, n].
 int sc_row_norm2(const void* D, float* norm2, int G, int n, int d, hipStream_t stream) {
   if (!D || !norm2 || G < 1 || n < 1 || d < 32 || d % 32) return 1;
   const long rows = (long)G * n;
-  const long blocks = (rows + 15) / 16;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(row_norm2_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
+  unsigned blocks;
+  if (!sc_grid(rows, 16, blocks)) return 1;
+  hipLaunchKernelGGL(row_norm2_kernel, dim3(blocks), dim3(256), 0, stream,
                      reinterpret_cast<const uint16_t*>(D), norm2, rows, d);
-  return launched();
+  return sc_launched();
 }
 
 // Rows row0 .. row0 + n_rows - 1 of the CSR (row_ptr int64 [G, ldp], col int32 [G, cap], val fp32 [G, cap])
@@ -276,14 +264,14 @@ int sc_active_capacity(const long* row_ptr, const int* col, const float* val, co
   if (!row_ptr || !col || !val || !D || !norm2 || !qsum || !count || !skipped) return 1;
   if (G < 1 || n < 1 || d < 32 || d % 32 || n_rows < 0 || row0 < 0 || ldp < row0 + n_rows + 1 || cap < 1) return 1;
   if (n_rows == 0) return 0;
-  const long blocks = ((long)G * n_rows + IC_ROWS - 1) / IC_ROWS;
-  if (blocks > 0x7fffffffL) return 1;
+  unsigned blocks;
+  if (!sc_grid((long)G * n_rows, IC_ROWS, blocks)) return 1;
   auto kern = d <= 32 * IC_KS_REG ? active_capacity_kernel<true> : active_capacity_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * IC_ROWS), 0, stream, row_ptr, ldp, row0, n_rows, col,
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * IC_ROWS), 0, stream, row_ptr, ldp, row0, n_rows, col,
                      val, cap, reinterpret_cast<const uint16_t*>(D), norm2, nactive, G, n, d,
                      reinterpret_cast<unsigned long long*>(qsum), reinterpret_cast<unsigned long long*>(count),
                      reinterpret_cast<unsigned long long*>(skipped), entry_cap);
-  return launched();
+  return sc_launched();
 }
 
 }  // extern "C"

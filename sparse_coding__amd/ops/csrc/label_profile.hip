@@ -33,7 +33,7 @@
 //
 // Known weak spot: a feature that fires on one label only is one lane adding its entries in sequence, and a
 // feature that fires on every row is M sequential adds in one wave.
-#include "common.h"
+#include "code_lists.h"
 
 namespace scamd {
 
@@ -44,12 +44,10 @@ __global__ __launch_bounds__(64 * LP_WAVES) void csr_take_rows_kernel(
     const long* __restrict__ row_ptr, long ldp, long N, const int* __restrict__ col, const float* __restrict__ val,
     long cap_in, const long* __restrict__ index, long M, const long* __restrict__ out_ptr, int* __restrict__ ocol,
     float* __restrict__ oval, long cap_out, long work, int waves) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (provably wave-uniform)
-  if (wave >= waves) return;
-  const long id = (long)blockIdx.x * waves + wave;  // (g, i) flattened
-  if (id >= work) return;
-  const long g = id / M, i = id - g * M;
+  ListWalk w;  // id: (g, i) flattened
+  if (!list_walk(w, work, waves)) return;
+  const int lane = w.lane;
+  const long g = w.id / M, i = w.id - g * M;
   const long r = index[i];
   if (r < 0 || r >= N) return;
   const long plo = row_ptr[g * ldp + r], phi = row_ptr[g * ldp + r + 1];
@@ -66,12 +64,6 @@ __global__ __launch_bounds__(64 * LP_WAVES) void csr_take_rows_kernel(
       oval[g * cap_out + pos] = val[q];
     }
   }
-}
-
-// The stored part [lo, hi) of list f of a model whose pointers are `cp` (0 <= lo <= hi <= cap whatever they hold).
-__device__ __forceinline__ void lp_list(const long* __restrict__ cp, int f, long cap, long& lo, long& hi) {
-  lo = min(max(cp[f], 0l), cap);
-  hi = min(max(cp[f + 1], lo), cap);
 }
 
 // Position of the k-th (from 0) set bit of `bits`; k < popcount(bits).
@@ -125,20 +117,12 @@ __device__ __forceinline__ bool lp_beats(const LpRun& x, const LpRun& c) {
 
 // Insert the wave-uniform run x into the K sorted slots; one that does not beat slot K - 1 changes nothing.
 template <int RANK>
-__device__ __forceinline__ void lp_insert(LpRun& cur, const LpRun& x, int K, int lane) {
-  const unsigned long long kmask = K >= 64 ? ~0ull : (1ull << K) - 1ull;
-  const int pos = __popcll(__ballot(!lp_beats<RANK>(x, cur)) & kmask);  // (the slots that stay ahead: a prefix)
-  LpRun up;
-  up.label = __shfl_up(cur.label, 1, 64);
-  up.cnt = __shfl_up(cur.cnt, 1, 64);
-  up.mx = __shfl_up(cur.mx, 1, 64);
-  up.sum = __shfl_up(cur.sum, 1, 64);
-  if (pos < K) {  // (field by field: a select between whole structs goes through memory)
-    cur.label = lane == pos ? x.label : lane > pos ? up.label : cur.label;
-    cur.cnt = lane == pos ? x.cnt : lane > pos ? up.cnt : cur.cnt;
-    cur.mx = lane == pos ? x.mx : lane > pos ? up.mx : cur.mx;
-    cur.sum = lane == pos ? x.sum : lane > pos ? up.sum : cur.sum;
-  }
+__device__ __forceinline__ void insert_run(LpRun& cur, const LpRun& x, int K, int lane) {
+  const int pos = insert_pos(!lp_beats<RANK>(x, cur), K);  // (the slots that stay ahead: a prefix)
+  insert_take(cur.label, x.label, pos, K, lane);  // (field by field: a select between whole structs goes
+  insert_take(cur.cnt, x.cnt, pos, K, lane);      // through memory)
+  insert_take(cur.mx, x.mx, pos, K, lane);
+  insert_take(cur.sum, x.sum, pos, K, lane);
 }
 
 // A finished wave-uniform run: into the totals, and into the winners if it beats slot m - 1.
@@ -148,18 +132,7 @@ __device__ __forceinline__ void lp_finish(const LpRun& x, LpRun& top, double& to
   tot = tot + x.sum;
   nl += 1;
   if (lane == 0) csq += (long)x.cnt * x.cnt;
-  if (lp_beats<RANK>(x, lp_bcast(top, m - 1))) lp_insert<RANK>(top, x, m, lane);
-}
-
-// Entry b + lane of a list that ends at hi: (row, code), or (-1, 0) past the end (row -1 is no valid row).
-__device__ __forceinline__ void lp_load(const int* __restrict__ row, const float* __restrict__ val, long b, long hi,
-                                        int lane, int& r, float& v) {
-  r = -1;
-  v = 0.f;
-  if (b + lane < hi) {
-    r = row[b + lane];
-    v = val[b + lane];
-  }
+  if (lp_beats<RANK>(x, lp_bcast(top, m - 1))) insert_run<RANK>(top, x, m, lane);
 }
 
 __device__ __forceinline__ int lp_label(const int* __restrict__ lab, int r, int M) {
@@ -172,14 +145,13 @@ __global__ __launch_bounds__(64 * LP_WAVES) void label_profile_kernel(
     int n, const int* __restrict__ lab, int M, int m, int waves, long* __restrict__ n_entries,
     int* __restrict__ n_labels, long* __restrict__ count_sq, double* __restrict__ total, int* __restrict__ top_label,
     int* __restrict__ top_count, double* __restrict__ top_sum, float* __restrict__ top_max) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (provably wave-uniform)
-  if (wave >= waves) return;
-  const long id = (long)blockIdx.x * waves + wave;  // (g, f) flattened
-  if (id >= lists) return;
-  const int g = (int)(id / n), f = (int)(id - (long)g * n);
+  ListWalk w;
+  if (!list_walk(w, lists, waves)) return;
+  w.split(n);
+  const int lane = w.lane, g = w.g;
+  const long id = w.id;
   long lo, hi;
-  lp_list(col_ptr + (long)g * (n + 1), f, cap, lo, hi);
+  list_bounds(col_ptr + (long)g * (n + 1), w.f, cap, lo, hi);
   row += (long)g * cap;
   val += (long)g * cap;
 
@@ -200,12 +172,12 @@ __global__ __launch_bounds__(64 * LP_WAVES) void label_profile_kernel(
 
   int r0, r1, r2, l0, l1;
   float v0, v1, v2;
-  lp_load(row, val, lo, hi, lane, r0, v0);
-  lp_load(row, val, lo + 64, hi, lane, r1, v1);
+  list_load(row, val, lo, hi, lane, r0, v0);
+  list_load(row, val, lo + 64, hi, lane, r1, v1);
   l0 = lp_label(lab, r0, M);
   for (long b = lo; b < hi; b += 64) {
     l1 = lp_label(lab, r1, M);
-    lp_load(row, val, b + 128, hi, lane, r2, v2);
+    list_load(row, val, b + 128, hi, lane, r2, v2);
 
     const bool valid = (unsigned)r0 < (unsigned)M;
     const unsigned long long vmask = __ballot(valid);
@@ -255,7 +227,7 @@ __global__ __launch_bounds__(64 * LP_WAVES) void label_profile_kernel(
       for (unsigned long long todo = fin & __ballot(lp_beats<RANK>(me, lp_bcast(top, m - 1))); todo;) {
         const int i = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
         todo &= todo - 1ull;
-        lp_insert<RANK>(top, lp_bcast(me, i), m, lane);
+        insert_run<RANK>(top, lp_bcast(me, i), m, lane);
       }
       open = lp_bcast(me, ns - 1);
     }
@@ -267,8 +239,7 @@ __global__ __launch_bounds__(64 * LP_WAVES) void label_profile_kernel(
   }
   if (open.cnt > 0) lp_finish<RANK>(open, top, tot, nl, csq, m, lane);
 
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) csq += __shfl_xor(csq, o, 64);  // (integers: any order)
+  csq = wave_sum_xor<true>(csq);  // (integers: any order)
   if (lane == 0) {
     n_entries[id] = ne;
     n_labels[id] = nl;
@@ -289,8 +260,6 @@ __global__ __launch_bounds__(64 * LP_WAVES) void label_profile_kernel(
 
 using namespace scamd;
 
-static int lp_launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 extern "C" {
 
 // Rows index[0 .. M) (int64, each in [0, N)) of the CSR codes row_ptr int64 [G, ldp] / col int32 / val fp32
@@ -302,11 +271,11 @@ int sc_csr_take_rows(const long* row_ptr, const int* col, const float* val, cons
   if (!row_ptr || !col || !val || !index || !out_ptr || !ocol || !oval) return 1;
   if (G < 1 || N < 1 || ldp < N + 1 || cap_in < 1 || M < 1 || cap_out < 1 || waves < 1 || waves > LP_WAVES) return 1;
   const long work = (long)G * M;
-  const long blocks = (work + waves - 1) / waves;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(csr_take_rows_kernel, dim3((unsigned)blocks), dim3(64 * waves), 0, stream, row_ptr, ldp, N, col,
+  unsigned blocks;
+  if (!sc_grid(work, waves, blocks)) return 1;
+  hipLaunchKernelGGL(csr_take_rows_kernel, dim3(blocks), dim3(64 * waves), 0, stream, row_ptr, ldp, N, col,
                      val, cap_in, index, M, out_ptr, ocol, oval, cap_out, work, waves);
-  return lp_launched();
+  return sc_launched();
 }
 
 // The label profile of every (g, f) list of the feature-major codes (col_ptr int64 [G, n + 1], row int32 / val
@@ -323,16 +292,16 @@ int sc_label_profile(const long* col_ptr, const int* row, const float* val, cons
       rank < 0 || rank > 1 || waves < 1 || waves > LP_WAVES)
     return 1;
   const long lists = (long)G * n;
-  const long blocks = (lists + waves - 1) / waves;
-  if (blocks > 0x7fffffffL) return 1;
-  const dim3 grid((unsigned)blocks), block(64 * waves);
+  unsigned blocks;
+  if (!sc_grid(lists, waves, blocks)) return 1;
+  const dim3 grid(blocks), block(64 * waves);
   if (rank == 0)
     hipLaunchKernelGGL(label_profile_kernel<0>, grid, block, 0, stream, col_ptr, row, val, cap, lists, n, lab, (int)M,
                        m, waves, n_entries, n_labels, count_sq, total, top_label, top_count, top_sum, top_max);
   else
     hipLaunchKernelGGL(label_profile_kernel<1>, grid, block, 0, stream, col_ptr, row, val, cap, lists, n, lab, (int)M,
                        m, waves, n_entries, n_labels, count_sq, total, top_label, top_count, top_sum, top_max);
-  return lp_launched();
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -124,7 +124,7 @@ int sc_row_sqerr(const void* r, float* err, int G, int B, int d, long N, long of
   const long rows = (long)G * B;
   hipLaunchKernelGGL(row_sqerr_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream,
                      reinterpret_cast<const uint16_t*>(r), err, rows, B, d, N, off);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 static int launch_resample(const ResampleArgs& a, int P, hipStream_t stream) {
@@ -138,7 +138,7 @@ static int launch_resample(const ResampleArgs& a, int P, hipStream_t stream) {
     default: return 1;
   }
 #undef SC_RESAMPLE
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 int sc_resample_rows(const int* dead_idx, const long* src_idx, const int* cnt, int P, const void* rows, long N,

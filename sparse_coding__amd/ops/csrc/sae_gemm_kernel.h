@@ -1232,7 +1232,7 @@ int launch(int epi, bool ak, bool bk, GemmParams p, int nprob, hipStream_t strea
     default: return 2;
   }
 #undef SC_L
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 

@@ -100,8 +100,6 @@ __global__ __launch_bounds__(64 * SC_ROWS) void code_rows_kernel(const uint16_t*
 
 using namespace scamd;
 
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 static bool codes_ok(const void* c, int G, int B, int n) {
   return c && G >= 1 && B >= 128 && B % 128 == 0 && n >= 128 && n % 128 == 0 &&
          (long)G * B / SC_ROWS <= 0x7fffffffL;
@@ -115,7 +113,7 @@ int sc_code_row_counts(const void* c, int* nnz, int G, int B, int n, hipStream_t
   hipLaunchKernelGGL(code_rows_kernel<false>, dim3((unsigned)((long)G * B / SC_ROWS)), dim3(64 * SC_ROWS), 0,
                      stream, reinterpret_cast<const uint16_t*>(c), B, n, nnz, nullptr, 0L, 0L, nullptr, nullptr,
                      0L);
-  return launched();
+  return sc_launched();
 }
 
 // row_ptr int64 [G, ldp]: row r of model g starts at row_ptr[g, row0 + r]; col int32 [G, cap], val fp32 [G, cap].
@@ -125,7 +123,7 @@ int sc_code_compact(const void* c, const long* row_ptr, int* col, float* val, in
   hipLaunchKernelGGL(code_rows_kernel<true>, dim3((unsigned)((long)G * B / SC_ROWS)), dim3(64 * SC_ROWS), 0,
                      stream, reinterpret_cast<const uint16_t*>(c), B, n, nullptr, row_ptr, ldp, row0, col, val,
                      cap);
-  return launched();
+  return sc_launched();
 }
 
 }  // extern "C"

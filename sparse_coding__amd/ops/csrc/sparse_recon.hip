@@ -38,7 +38,7 @@
 // column is in [0, lim), lim = n or min(n, nactive[g]).  All columns are checked before the first gather;
 // a gathered column is one of the checked ones.  Every store is behind the row's id < G n_rows test and
 // its own j <= J / j < 3 bound.  The only atomic is the 64-bit integer add on skipped.
-#include "sr_rows.h"  // the layout, load / axpy / norm helpers and the skip rule (shared with attribution.hip)
+#include "sr_rows.h"  // the layout, load / axpy / norm helpers (shared with attribution.hip); brings code_lists.h
 
 namespace scamd {
 
@@ -48,10 +48,7 @@ __device__ __forceinline__ unsigned long long sr_max64(unsigned long long v) {
     const unsigned long long u = __shfl_xor(v, o, 64);
     v = u > v ? u : v;
   }
-  // every lane holds the maximum: hand it on as a wave-uniform value
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
+  return uniform_u64(v);  // (every lane holds the maximum)
 }
 
 __device__ __forceinline__ unsigned long long sr_key(float c, int col) {
@@ -71,12 +68,11 @@ __global__ __launch_bounds__(64 * SR_ROWS) void recon_curve_kernel(
   const int g = (int)(id / n_rows);
   const long r = id - (long)g * n_rows;
   const long lo = row_ptr[(long)g * ldp + row0 + r], hi = row_ptr[(long)g * ldp + row0 + r + 1];
-  int lim = n;
-  if (nactive) lim = min(n, max(0, nactive[g]));
+  const int lim = live_limit(nactive, g, n);
   col += (long)g * cap;
   val += (long)g * cap;
   float* o = out + id * (long)(J + 1);
-  if (!sr_row_ok(lo, hi, cap, n, lim, col, lane)) {
+  if (!csr_row_ok(lo, hi, cap, n, lim, col, lane)) {
     for (int j = lane; j <= J; j += 64) o[j] = 0.f;
     if (lane == 0) atomicAdd(skipped + g, 1ull);
     return;
@@ -138,12 +134,11 @@ __global__ __launch_bounds__(64 * SR_ROWS) void recon_split_kernel(
   const int g = (int)(id / n_rows);
   const long r = id - (long)g * n_rows;
   const long lo = row_ptr[(long)g * ldp + row0 + r], hi = row_ptr[(long)g * ldp + row0 + r + 1];
-  int lim = n;
-  if (nactive) lim = min(n, max(0, nactive[g]));
+  const int lim = live_limit(nactive, g, n);
   col += (long)g * cap;
   val += (long)g * cap;
   float* o = out + id * 3;
-  if (!sr_row_ok(lo, hi, cap, n, lim, col, lane)) {
+  if (!csr_row_ok(lo, hi, cap, n, lim, col, lane)) {
     if (lane < 3) o[lane] = 0.f;
     if (lane == 0) atomicAdd(skipped + g, 1ull);
     return;
@@ -204,8 +199,6 @@ __global__ __launch_bounds__(64 * SR_ROWS) void recon_split_kernel(
 
 using namespace scamd;
 
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 extern "C" {
 
 // Rows row0 .. row0 + n_rows - 1 of the CSR (row_ptr int64 [G, ldp], col int32 [G, cap], val fp32 [G, cap])
@@ -223,7 +216,7 @@ int sc_recon_curve(const long* row_ptr, const int* col, const float* val, const 
                                          ldp, row0, n_rows, col, val, cap, reinterpret_cast<const uint16_t*>(D),
                                          reinterpret_cast<const uint16_t*>(x), x_stride, nactive, G, n, J, out,
                                          reinterpret_cast<unsigned long long*>(skipped)))
-  return launched();
+  return sc_launched();
 }
 
 // As sc_recon_curve; keep uint32 [G, ceil(n / 32)] or null; out fp32 [G, n_rows, 3] is written.
@@ -245,7 +238,7 @@ int sc_recon_split(const long* row_ptr, const int* col, const float* val, const 
     SR_DISPATCH(d / 64, SR_SPLIT(false))
   }
 #undef SR_SPLIT
-  return launched();
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -1,9 +1,9 @@
 // Row helpers shared by the kernels that keep one bf16 row of d = 64 P elements per wave in registers
-// (sparse_recon.hip, attribution.hip): the lane / element layout, the packed row load, the fp32 axpy, the
-// squared norm and the skip rule of a CSR row.  The fp32 orders written here are contracts: the oracles
-// emulate them and the tests compare bits.
+// (sparse_recon.hip, attribution.hip): the lane / element layout, the packed row load, the fp32 axpy and the
+// squared norm.  The fp32 orders written here are contracts: the oracles emulate them and the tests compare
+// bits.  The skip rule of a CSR row and the live column limit come with code_lists.h.
 #pragma once
-#include "common.h"
+#include "code_lists.h"
 
 namespace scamd {
 
@@ -60,24 +60,7 @@ __device__ __forceinline__ float sr_norm2(const float (&r)[P]) {
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < P; ++i) s = fmaf(r[i], r[i], s);
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-
-// The skip rule (wave-uniform result).  `col` is the model's column array.
-__device__ __forceinline__ bool sr_row_ok(long lo, long hi, long cap, int n, int lim, const int* __restrict__ col,
-                                          int lane) {
-  bool ok = lo >= 0 && hi >= lo && hi <= cap && hi - lo <= (long)n;
-  if (ok) {
-    bool bad = false;
-    for (long e = lo + lane; e < hi; e += 64) {
-      const int j = col[e];
-      bad |= (j < 0) | (j >= lim);
-    }
-    ok = __ballot(bad) == 0ull;
-  }
-  return ok;
+  return wave_sum_xor<true>(s);
 }
 
 }  // namespace scamd

@@ -73,7 +73,7 @@ int sc_synth_codes(const float* probs, void* out, long B, int n, unsigned long l
   const long total = B * (n / 4);
   hipLaunchKernelGGL(synth_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, probs,
                      reinterpret_cast<uint16_t*>(out), B, n, (uint32_t)seed, (uint32_t)(seed >> 32), row0);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -26,11 +26,6 @@
 
 namespace scamd {
 
-__device__ __forceinline__ uint32_t order_key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // larger float -> larger key
-}
-
 // Exact per-row top-k by radix select on the orderable bit pattern: three digit
 // passes (11, 11, 10 bits).  Each pass builds the histogram of the still-eligible
 // keys in four per-wave copies (a quarter of the LDS-atomic contention of one
@@ -1312,9 +1307,6 @@ __global__ __launch_bounds__(256) void topk_scatter_kernel(const int* __restrict
 
 using namespace scamd;
 
-// 0 when the launches before it were accepted, 3 otherwise
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 extern "C" {
 
 int sc_topk_select(const float* scores, const int* k, int* idx, float* val, int G, int B, int n, int kmax,
@@ -1326,7 +1318,7 @@ int sc_topk_select(const float* scores, const int* k, int* idx, float* val, int 
 #define SC_W(P) \
     if (n <= 64 * P) { hipLaunchKernelGGL((topk_wave_kernel<P>), wgrid, dim3(256), 0, stream, scores, k, idx, val, rows, B, n, \
                                           kmax, absolute, relu); \
-      return hipGetLastError() == hipSuccess ? 0 : 3; }
+      return sc_launched(); }
     SC_W(16) SC_W(32) SC_W(64)
 #undef SC_W
   }
@@ -1336,7 +1328,7 @@ int sc_topk_select(const float* scores, const int* k, int* idx, float* val, int 
 #define SC_BK(P) \
     if (n <= 256 * P) { hipLaunchKernelGGL((topk_block_kernel<P>), bgrid, dim3(256), 0, stream, scores, k, idx, val, B, n, \
                                            kmax, absolute, relu, bracket); \
-      return hipGetLastError() == hipSuccess ? 0 : 3; }
+      return sc_launched(); }
     SC_BK(24) SC_BK(32) SC_BK(48) SC_BK(64)
 #undef SC_BK
   }
@@ -1344,7 +1336,7 @@ int sc_topk_select(const float* scores, const int* k, int* idx, float* val, int 
   dim3 grid((unsigned)G * B);
 #define SC_T(P) \
   if (per <= P) { hipLaunchKernelGGL((topk_select_kernel<P>), grid, dim3(256), 0, stream, scores, k, idx, val, B, n, kmax, absolute, relu); \
-    return hipGetLastError() == hipSuccess ? 0 : 3; }
+    return sc_launched(); }
   SC_T(4) SC_T(8) SC_T(16) SC_T(24) SC_T(32) SC_T(48) SC_T(64)
 #undef SC_T
   return 1;
@@ -1363,7 +1355,7 @@ int sc_topk_select_bf16(const void* scores, const int* k, int* idx, float* val, 
 #define SC_B16(P) \
   if (n <= 256 * P) { hipLaunchKernelGGL((topk_bf16_kernel<P>), grid, dim3(256), 0, stream, S, k, idx, val, B, n, kmax, \
                                          absolute, relu, Xp, sx, Dp, d); \
-    return hipGetLastError() == hipSuccess ? 0 : 3; }
+    return sc_launched(); }
   SC_B16(8) SC_B16(16) SC_B16(24) SC_B16(32) SC_B16(48) SC_B16(64)
 #undef SC_B16
   return 1;
@@ -1380,7 +1372,7 @@ int sc_topk_decode_grad(const int* idx, const float* val, const int* k, const vo
       reinterpret_cast<const uint16_t*>(D), reinterpret_cast<const uint16_t*>(X), sx, reinterpret_cast<uint16_t*>(R), \
       row_se, reinterpret_cast<uint16_t*>(codebuf), reinterpret_cast<uint16_t*>(dscbuf), G, B, n, d, kmax, dscv, prev_idx, \
       g_dense0); \
-    return launched(); }
+    return sc_launched(); }
   SC_D(1) SC_D(2) SC_D(3) SC_D(4) SC_D(8) SC_D(16)
 #undef SC_D
   return 1;
@@ -1408,7 +1400,7 @@ int sc_topk_slot_lists(const int* idx, const int* k, int* cnt, int* offs, int* c
   } else {
     return 1;
   }
-  return launched();
+  return sc_launched();
 }
 
 // G[0 .. Gs) rows of the weight gradient from the sorted slot lists (see the kernel).
@@ -1419,7 +1411,7 @@ int sc_topk_sparse_wgrad(const int* perm, const int* offs, const float* val, con
 #define SC_SW(V) \
   if (d == 256 * V) { hipLaunchKernelGGL((topk_sparse_wgrad_kernel<V>), grid, dim3(256), 0, stream, perm, offs, val, dscv, \
       reinterpret_cast<const uint16_t*>(R), reinterpret_cast<const uint16_t*>(X), sx, Gout, Gs, B, n, kmax, alpha, out_bf16); \
-    return launched(); }
+    return sc_launched(); }
   SC_SW(1) SC_SW(2) SC_SW(3) SC_SW(4)
 #undef SC_SW
   return 1;
@@ -1430,14 +1422,14 @@ int sc_topk_scatter(const int* idx, const float* val, const int* k, void* code, 
   const long total = rows * kmax;
   hipLaunchKernelGGL(topk_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, idx, val, k,
                      reinterpret_cast<uint16_t*>(code), rows, rows_per_model, n, kmax);
-  return launched();
+  return sc_launched();
 }
 
 int sc_topk_clear(const int* idx, void* a, void* b, long rows, int n, int kmax, hipStream_t stream) {
   const long total = rows * kmax;
   hipLaunchKernelGGL(topk_clear_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, idx,
                      reinterpret_cast<uint16_t*>(a), reinterpret_cast<uint16_t*>(b), rows, n, kmax);
-  return launched();
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 //   equal value never displaces a listed one).  Every feature is owned by one wave, the cross-lane
 //   sums are one fixed butterfly and the lists are merged in row order: no floating-point atomics,
 //   the same bits every run and under any chunking of the calls.
-#include "common.h"
+#include "code_lists.h"
 
 namespace scamd {
 
@@ -45,23 +45,16 @@ __global__ __launch_bounds__(256) void topk_pick_count_kernel(const int* __restr
     if (hist[j]) atomicAdd(&counts[(long)g * n + j], (unsigned long long)hist[j]);
 }
 
-// Fixed-shape wave-wide sum of a double (xor butterfly: every lane ends with the same bits).
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void topk_pick_stats_kernel(const int* __restrict__ perm, const int* __restrict__ offs,
                                                               const float* __restrict__ val, double* __restrict__ acc,
                                                               float* __restrict__ mx, float* __restrict__ top_vals,
                                                               long long* __restrict__ top_rows, int G, int B, int n,
                                                               int kmax, int K, long long row0, long perm_len) {
-  const int lane = threadIdx.x & 63;
-  const long list = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long lists = (long)G * n;
-  if (list >= lists) return;
-  const int g = (int)(list / n), j = (int)(list - (long)g * n);
+  ListWalk w;
+  if (!list_walk<4>(w, (long)G * n)) return;
+  w.split(n);
+  const int lane = w.lane, g = w.g, j = w.f;
+  const long list = w.id;
   const int beg = offs[list];
   int L = min(max(offs[list + 1] - beg, 0), B);  // (a row picks a feature at most once)
   if (beg < 0 || (long)beg + L > perm_len) L = 0;  // (offsets that are no slot lists: read nothing)
@@ -120,11 +113,11 @@ __global__ __launch_bounds__(256) void topk_pick_stats_kernel(const int* __restr
       }
     }
   }
-  cnt = wave_sum_f64(cnt);
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
-  s3 = wave_sum_f64(s3);
-  s4 = wave_sum_f64(s4);
+  cnt = wave_sum_xor<false>(cnt);
+  s1 = wave_sum_xor<false>(s1);
+  s2 = wave_sum_xor<false>(s2);
+  s3 = wave_sum_xor<false>(s3);
+  s4 = wave_sum_xor<false>(s4);
   vmax = wave_max(vmax);
   if (lane < 5) {
     const double add = lane == 0 ? cnt : lane == 1 ? s1 : lane == 2 ? s2 : lane == 3 ? s3 : s4;
@@ -155,7 +148,7 @@ int sc_topk_pick_counts(const int* idx, const float* val, const int* k, long* co
   const size_t lds = (size_t)n * sizeof(int);
   hipLaunchKernelGGL(topk_pick_count_kernel, grid, dim3(256), lds, stream, idx, val, k,
                      reinterpret_cast<unsigned long long*>(counts), B, n, kmax, rpb, step_dev, every);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 // perm / offs: the sorted slot lists of all G models (sc_topk_slot_lists with Gs = G); acc fp64 [G, 5, n],
@@ -169,11 +162,11 @@ int sc_topk_pick_stats(const int* perm, const int* offs, const float* val, doubl
     return 1;
   if (K > 0 && (!top_vals || !top_rows)) return 1;
   if ((long)G * B * kmax >= (1l << 31)) return 1;
-  const long lists = (long)G * n;
-  if ((lists + 3) / 4 > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(topk_pick_stats_kernel, dim3((unsigned)((lists + 3) / 4)), dim3(256), 0, stream, perm, offs, val,
+  unsigned blocks;
+  if (!sc_grid((long)G * n, 4, blocks)) return 1;
+  hipLaunchKernelGGL(topk_pick_stats_kernel, dim3(blocks), dim3(256), 0, stream, perm, offs, val,
                      acc, mx, top_vals, reinterpret_cast<long long*>(top_rows), G, B, n, kmax, K, (long long)row0, perm_len);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 //                       (col_ptr int64 [G, n + 1], row int32 / val fp32 [G, cap], rows ascending in a list): the
 //                       list ordered by KEY ascending, then row ascending, written to vrow / vval [G, cap_out]
 //                       at the list's own positions.  KEY is the order-preserving map of the fp32 bit pattern
-//                       (co_order of coactivation.hip): a total order on all bit patterns, so -0.0 sorts before
+//                       (order_key of common.h): a total order on all bit patterns, so -0.0 sorts before
 //                       +0.0 and every NaN has its place.  Rows are distinct in a list and the sort is stable on
 //                       an input with ascending rows: the output is unique, whatever the launch geometry.
 //       L <= 64     a rank sort in registers: every lane counts the entries that go before its own.
@@ -37,22 +37,19 @@
 // Known weak spot: one wave per list whatever its length.  A feature that fires on every row is one wave walking
 // N entries once per executed pass (at most five times) in the sort and once, entry by entry, in the AUROC walk;
 // a block-wide path for long lists is not built.
-#include "common.h"
+#include "code_lists.h"
 
 namespace scamd {
 
 constexpr int VO_WAVES = 4;   // waves per block
 constexpr int VO_MAX_K = 32;  // concepts per flag word
 
-__device__ __forceinline__ void vo_list(const long* __restrict__ cp, int f, long lim, long& lo, long& hi) {
-  lo = min(max(cp[f], 0l), lim);
-  hi = min(max(cp[f + 1], lo), lim);
+// list_bounds with provably wave-uniform results.
+__device__ __forceinline__ void vo_bounds(const long* __restrict__ cp, int f, long lim, long& lo, long& hi) {
+  list_bounds(cp, f, lim, lo, hi);
   lo = __builtin_amdgcn_readfirstlane((int)lo);  // (lim < 2^31; wave-uniform: the loops below branch in scalars)
   hi = __builtin_amdgcn_readfirstlane((int)hi);
 }
-
-// Order-preserving map of the fp32 bit pattern (co_order of coactivation.hip).
-__device__ __forceinline__ uint32_t vo_key(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 
 // Where a pass reads from or writes to: separate row / code-bit arrays, or (row, code bits) pairs.
 struct VoBuf {
@@ -85,14 +82,12 @@ __global__ __launch_bounds__(64 * VO_WAVES) void list_sort_kernel(
     const long* __restrict__ col_ptr, const int* row, const uint32_t* val, long cap, long lim, long lists, int n,
     int waves, int* vrow, uint32_t* vval, long cap_out, int2* tmp) {
   __shared__ uint32_t hist_all[VO_WAVES][4][256];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (provably wave-uniform)
-  if (wave >= waves) return;
-  const long id = (long)blockIdx.x * waves + wave;  // (g, f) flattened
-  if (id >= lists) return;
-  const int g = (int)(id / n), f = (int)(id - (long)g * n);
+  ListWalk w;
+  if (!list_walk(w, lists, waves)) return;
+  w.split(n);
+  const int lane = w.lane, wave = w.wave, g = w.g;
   long lo, hi;
-  vo_list(col_ptr + (long)g * (n + 1), f, lim, lo, hi);
+  vo_bounds(col_ptr + (long)g * (n + 1), w.f, lim, lo, hi);
   const long L = hi - lo;
   if (L <= 0) return;
   const VoBuf in = {const_cast<int*>(row) + (long)g * cap, const_cast<uint32_t*>(val) + (long)g * cap, nullptr};
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(64 * VO_WAVES) void list_sort_kernel(
     uint32_t b = 0, key = 0;
     if (lane < L) {
       vo_read(in, lo + lane, r, b);
-      key = vo_key(b);
+      key = order_key(b);
     }
     int rank = 0;
     for (int j = 0; j < (int)L; ++j) {
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(64 * VO_WAVES) void list_sort_kernel(
   uint32_t(*hist)[256] = hist_all[wave];
   for (int i = lane; i < 4 * 256; i += 64) (&hist[0][0])[i] = 0u;
   for (long e = lo + lane; e < hi; e += 64) {
-    const uint32_t key = vo_key(in.bits[e]);
+    const uint32_t key = order_key(in.bits[e]);
     atomicAdd(&hist[0][key & 255u], 1u);
     atomicAdd(&hist[1][(key >> 8) & 255u], 1u);
     atomicAdd(&hist[2][(key >> 16) & 255u], 1u);
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(64 * VO_WAVES) void list_sort_kernel(
       const uint32_t b0 = b1;
       const bool valid = b + lane < hi;
       if (b + 64 + lane < hi) vo_read(src, b + 64 + lane, r1, b1);  // (the next chunk, while this one is ranked)
-      const uint32_t dg = (vo_key(b0) >> shift) & 255u;
+      const uint32_t dg = (order_key(b0) >> shift) & 255u;
       unsigned long long peers = __ballot(valid);
 #pragma unroll
       for (int bit = 0; bit < 8; ++bit) {
@@ -195,16 +190,6 @@ __global__ __launch_bounds__(64 * VO_WAVES) void list_sort_kernel(
   }
 }
 
-__device__ __forceinline__ void vo_load(const int* __restrict__ row, const float* __restrict__ val, long b, long hi,
-                                        int lane, int& r, float& v) {
-  r = -1;
-  v = 0.f;
-  if (b + lane < hi) {
-    r = row[b + lane];
-    v = val[b + lane];
-  }
-}
-
 __device__ __forceinline__ uint32_t vo_flags(const int* __restrict__ flags, int r, int N) {
   return (unsigned)r < (unsigned)N ? (uint32_t)flags[r] : 0u;
 }
@@ -212,14 +197,13 @@ __device__ __forceinline__ uint32_t vo_flags(const int* __restrict__ flags, int 
 __global__ __launch_bounds__(64 * VO_WAVES) void list_auroc_kernel(
     const long* __restrict__ col_ptr, const int* __restrict__ row, const float* __restrict__ val, long cap, long lists,
     int n, const int* __restrict__ flags, int N, int K, int waves, int* __restrict__ pos_in, long* __restrict__ u2) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (provably wave-uniform)
-  if (wave >= waves) return;
-  const long id = (long)blockIdx.x * waves + wave;  // (g, f) flattened
-  if (id >= lists) return;
-  const int g = (int)(id / n), f = (int)(id - (long)g * n);
+  ListWalk w;
+  if (!list_walk(w, lists, waves)) return;
+  w.split(n);
+  const int lane = w.lane, g = w.g;
+  const long id = w.id;
   long lo, hi;
-  vo_list(col_ptr + (long)g * (n + 1), f, cap, lo, hi);
+  vo_bounds(col_ptr + (long)g * (n + 1), w.f, cap, lo, hi);
   row += (long)g * cap;
   val += (long)g * cap;
 
@@ -232,12 +216,12 @@ __global__ __launch_bounds__(64 * VO_WAVES) void list_auroc_kernel(
   int r0, r1, r2;
   float v0, v1, v2;
   uint32_t w0, w1;
-  vo_load(row, val, lo, hi, lane, r0, v0);
-  vo_load(row, val, lo + 64, hi, lane, r1, v1);
+  list_load(row, val, lo, hi, lane, r0, v0);
+  list_load(row, val, lo + 64, hi, lane, r1, v1);
   w0 = vo_flags(flags, r0, N);
   for (long b = lo; b < hi; b += 64) {
     w1 = vo_flags(flags, r1, N);
-    vo_load(row, val, b + 128, hi, lane, r2, v2);
+    list_load(row, val, b + 128, hi, lane, r2, v2);
     unsigned long long todo = __ballot((unsigned)r0 < (unsigned)N);
     while (todo) {
       const int j = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
@@ -274,8 +258,6 @@ __global__ __launch_bounds__(64 * VO_WAVES) void list_auroc_kernel(
 
 using namespace scamd;
 
-static int vo_launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-
 extern "C" {
 
 // Every (g, f) list of the feature-major codes (col_ptr int64 [G, n + 1], row int32 / val fp32 [G, cap]) ordered
@@ -290,12 +272,12 @@ int sc_list_sort_by_value(const long* col_ptr, const int* row, const float* val,
     return 1;
   if ((const void*)row == (const void*)vrow || (const void*)val == (const void*)vval) return 1;
   const long lists = (long)G * n;
-  const long blocks = (lists + waves - 1) / waves;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(list_sort_kernel, dim3((unsigned)blocks), dim3(64 * waves), 0, stream, col_ptr, row,
+  unsigned blocks;
+  if (!sc_grid(lists, waves, blocks)) return 1;
+  hipLaunchKernelGGL(list_sort_kernel, dim3(blocks), dim3(64 * waves), 0, stream, col_ptr, row,
                      (const uint32_t*)val, cap, min(cap, cap_out), lists, n, waves, vrow, (uint32_t*)vval, cap_out,
                      (int2*)tmp);
-  return vo_launched();
+  return sc_launched();
 }
 
 // One walk per value-ordered list (col_ptr int64 [G, n + 1], vrow int32 / vval fp32 [G, cap]) against flags int32
@@ -307,11 +289,11 @@ int sc_list_auroc(const long* col_ptr, const int* vrow, const float* vval, const
       waves < 1 || waves > VO_WAVES)
     return 1;
   const long lists = (long)G * n;
-  const long blocks = (lists + waves - 1) / waves;
-  if (blocks > 0x7fffffffL) return 1;
-  hipLaunchKernelGGL(list_auroc_kernel, dim3((unsigned)blocks), dim3(64 * waves), 0, stream, col_ptr, vrow, vval, cap,
+  unsigned blocks;
+  if (!sc_grid(lists, waves, blocks)) return 1;
+  hipLaunchKernelGGL(list_auroc_kernel, dim3(blocks), dim3(64 * waves), 0, stream, col_ptr, vrow, vval, cap,
                      lists, n, flags, (int)N, K, waves, pos_in, u2);
-  return vo_launched();
+  return sc_launched();
 }
 
 }  // extern "C"

@@ -7,31 +7,13 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .interference import _buffer
+from ._args import INT32_MAX, _buffer, _csr, _lists
 
 MAX_K = 32               # largest Kt / Kr of ``fragment_examples``
 SEGMENT_ROWS = 1024      # default rows per segment of the transposition
 LDS_BINS = 8192          # default widest LDS histogram: 32 KiB of the CU's 160 KiB, five blocks stay co-resident
 MAX_LDS_BINS = 16384     # the kernels' own limit (64 KiB)
 MAX_SEGMENT_ROWS = 8192
-INT32_MAX = 2 ** 31 - 1
-
-
-def _csr(row_ptr, col, val, nactive):
-    if row_ptr.dim() != 2 or row_ptr.dtype != torch.int64 or not row_ptr.is_contiguous() or row_ptr.shape[1] < 2:
-        raise ValueError("row_ptr must be contiguous int64 [G, N + 1] with N >= 1")
-    G, dev = row_ptr.shape[0], row_ptr.device
-    if col.dim() != 2 or col.shape[0] != G:
-        raise ValueError(f"col must be int32 [{G}, cap]")
-    cap = col.shape[1]
-    _buffer("col", col, torch.int32, (G, cap), dev)
-    _buffer("val", val, torch.float32, (G, cap), dev)
-    if nactive is not None:
-        _buffer("nactive", nactive, torch.int32, (G,), dev)
-    N = row_ptr.shape[1] - 1
-    if N > INT32_MAX or cap > INT32_MAX:
-        raise ValueError(f"by_feature needs N < 2^31 and cap < 2^31 (got N={N}, cap={cap})")
-    return G, N, cap, dev
 
 
 def by_feature(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: int, *,
@@ -110,20 +92,6 @@ def by_feature(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: i
                                   _lib.ptr(oval), G, n, S, shift, tcap, ocap, st)
         _lib.check(rc, "sc_feature_order")
     return col_ptr, orow, oval, skipped
-
-
-def _lists(col_ptr, row, val):
-    if col_ptr.dim() != 2 or col_ptr.dtype != torch.int64 or not col_ptr.is_contiguous() or col_ptr.shape[1] < 2:
-        raise ValueError("col_ptr must be contiguous int64 [G, n + 1]")
-    G, n, dev = col_ptr.shape[0], col_ptr.shape[1] - 1, col_ptr.device
-    if row.dim() != 2 or row.shape[0] != G:
-        raise ValueError(f"row must be int32 [{G}, cap]")
-    cap = row.shape[1]
-    _buffer("row", row, torch.int32, (G, cap), dev)
-    _buffer("val", val, torch.float32, (G, cap), dev)
-    if cap == 0:
-        row, val = col_ptr.new_zeros(G, 1, dtype=torch.int32), col_ptr.new_zeros(G, 1, dtype=torch.float32)
-    return G, n, cap, dev, row, val
 
 
 def check_fragments(n_rows: int, fragment_len) -> int:

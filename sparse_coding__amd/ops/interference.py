@@ -7,20 +7,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-
-
-def _dictionary(D: torch.Tensor, what: str):
-    if D.dim() != 3 or D.dtype != torch.bfloat16 or not D.is_contiguous() or D.data_ptr() % 16:
-        raise ValueError(f"{what} needs a contiguous, 16-byte aligned bf16 dictionary [G, n, d]")
-    G, n, d = D.shape
-    if G < 1 or n < 1 or d < 32 or d % 32:
-        raise ValueError(f"{what} needs d % 32 == 0 (got n={n}, d={d})")
-    return G, n, d
-
-
-def _buffer(name: str, t: torch.Tensor, dtype, shape, device):
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
-        raise ValueError(f"{name} must be contiguous {dtype} {list(shape)} on the dictionary's device")
+from ._args import _buffer, _dictionary
 
 
 def row_norm2(D: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

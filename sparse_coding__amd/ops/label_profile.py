@@ -7,13 +7,10 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .feature_codes import _lists
-from .interference import _buffer
+from ._args import INT32_MAX, WAVES, _buffer, _lists, check_waves, out_buffers  # noqa: F401 (WAVES is public)
 
 MAX_M = 64                # most runs kept per feature: one slot per lane
 RANKS = ("sum", "count")
-WAVES = (1, 2, 4)         # waves per block
-INT32_MAX = 2 ** 31 - 1
 
 
 def check_m(m) -> int:
@@ -47,9 +44,7 @@ def label_profile(col_ptr: torch.Tensor, row: torch.Tensor, val: torch.Tensor, l
     sorted only gives more runs.  ``waves``: waves per block, 1, 2 or 4 -- the bits do not depend on it.
     ``out``: the eight buffers to fill.  One launch, one wave per list; nothing synchronises."""
     G, n, cap, dev, row_, val_ = _lists(col_ptr, row, val)
-    m, rank_by = check_m(m), check_rank(rank_by)
-    if waves not in WAVES:
-        raise ValueError(f"waves must be one of {WAVES}, got {waves!r}")
+    m, rank_by, waves = check_m(m), check_rank(rank_by), check_waves(waves)
     if lab.dim() != 1 or lab.shape[0] < 1:
         raise ValueError("lab must be int32 [M] with M >= 1")
     M = lab.shape[0]
@@ -60,14 +55,9 @@ def label_profile(col_ptr: torch.Tensor, row: torch.Tensor, val: torch.Tensor, l
             ("total", torch.float64, (G, n)), ("top_label", torch.int32, (G, n, m)),
             ("top_count", torch.int32, (G, n, m)), ("top_sum", torch.float64, (G, n, m)),
             ("top_max", torch.float32, (G, n, m)))
-    if out is None:
-        out = tuple(torch.empty(shape, device=dev, dtype=dt) for _, dt, shape in spec)
-    if len(out) != len(spec):
-        raise ValueError(f"out must hold the {len(spec)} buffers {[s[0] for s in spec]}")
-    for t, (name, dt, shape) in zip(out, spec):
-        _buffer(f"out {name}", t, dt, shape, dev)
+    out = out_buffers(spec, out, dev)
     rc = _lib.lib().sc_label_profile(_lib.ptr(col_ptr), _lib.ptr(row_), _lib.ptr(val_), _lib.ptr(lab),
-                                     *(_lib.ptr(t) for t in out), G, n, cap, M, m, RANKS.index(rank_by), int(waves),
+                                     *(_lib.ptr(t) for t in out), G, n, cap, M, m, RANKS.index(rank_by), waves,
                                      _lib.stream_handle())
     _lib.check(rc, "sc_label_profile")
-    return tuple(out)
+    return out

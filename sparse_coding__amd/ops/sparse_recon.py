@@ -7,50 +7,9 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .interference import _buffer
+from ._args import _buffer, _rows
 
 MAX_KEPT = 64   # largest J of ``recon_curve``
-
-
-def _dictionary(D: torch.Tensor, what: str):
-    if D.dim() != 3 or D.dtype != torch.bfloat16 or not D.is_contiguous() or D.data_ptr() % 16:
-        raise ValueError(f"{what} needs a contiguous, 16-byte aligned bf16 dictionary [G, n, d]")
-    G, n, d = D.shape
-    if G < 1 or n < 1 or d < 64 or d > 1024 or d % 64:
-        raise ValueError(f"{what} needs d % 64 == 0 and 64 <= d <= 1024 (got n={n}, d={d})")
-    return G, n, d
-
-
-def _rows(what, row_ptr, col, val, D, x, skipped, row0, n_rows, nactive):
-    """The checks both launches share; returns (G, n, d, cap, row0, n_rows, x_stride, col, val)."""
-    G, n, d = _dictionary(D, what)
-    dev = D.device
-    if row_ptr.dim() != 2 or row_ptr.dtype != torch.int64 or row_ptr.shape[0] != G or not row_ptr.is_contiguous() \
-            or row_ptr.device != dev:
-        raise ValueError(f"row_ptr must be contiguous int64 [{G}, *] on the dictionary's device")
-    if x.dim() not in (2, 3) or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.data_ptr() % 16 \
-            or x.device != dev or x.shape[-1] != d or (x.dim() == 3 and x.shape[0] != G):
-        raise ValueError(f"x must be contiguous, 16-byte aligned bf16 [rows, {d}] or [{G}, rows, {d}] on the "
-                         "dictionary's device")
-    row0 = int(row0)
-    n_rows = x.shape[-2] if n_rows is None else int(n_rows)
-    if n_rows != x.shape[-2]:
-        raise ValueError(f"x holds {x.shape[-2]} rows, the window has {n_rows}")
-    if row0 < 0 or n_rows < 0 or row_ptr.shape[1] < row0 + n_rows + 1:
-        raise ValueError(f"row_ptr holds {row_ptr.shape[1]} entries per model, rows {row0} .. {row0 + n_rows} "
-                         "are needed")
-    if col.dim() != 2 or col.shape[0] != G:
-        raise ValueError(f"col must be int32 [{G}, cap]")
-    cap = col.shape[1]
-    _buffer("col", col, torch.int32, (G, cap), dev)
-    _buffer("val", val, torch.float32, (G, cap), dev)
-    _buffer("skipped", skipped, torch.int64, (G,), dev)
-    if nactive is not None:
-        _buffer("nactive", nactive, torch.int32, (G,), dev)
-    if cap == 0:  # (no entry is stored: the kernel's skip rule passes only rows 0 .. 0 and reads no entry;
-        #            the placeholders stand in for the empty buffers' null pointers)
-        col, val = row_ptr.new_zeros(1, dtype=torch.int32), row_ptr.new_zeros(1, dtype=torch.float32)
-    return G, n, d, cap, row0, n_rows, (x.shape[1] * d if x.dim() == 3 else 0), col, val
 
 
 def recon_curve(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, D: torch.Tensor, x: torch.Tensor,

@@ -7,25 +7,15 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .feature_codes import _lists
-from .interference import _buffer
+from ._args import INT32_MAX, WAVES, _buffer, _lists, check_waves, out_buffers  # noqa: F401 (WAVES is public)
 
 MAX_CONCEPTS = 32         # concepts per flag word: one per bit of an int32
-WAVES = (1, 2, 4)         # waves per block
-INT32_MAX = 2 ** 31 - 1
 
 
 def check_concepts(n_concepts) -> int:
     if isinstance(n_concepts, bool) or int(n_concepts) != n_concepts or not 1 <= int(n_concepts) <= MAX_CONCEPTS:
         raise ValueError(f"n_concepts must be an integer in 1..{MAX_CONCEPTS}, got {n_concepts!r}")
     return int(n_concepts)
-
-
-def _waves(waves) -> int:
-    waves = 4 if waves is None else waves
-    if waves not in WAVES:
-        raise ValueError(f"waves must be one of {WAVES}, got {waves!r}")
-    return int(waves)
 
 
 def stored_ptr(col_ptr: torch.Tensor, lim: int) -> torch.Tensor:
@@ -50,7 +40,7 @@ def sort_lists(col_ptr: torch.Tensor, row: torch.Tensor, val: torch.Tensor, *,
     be the inputs.  One launch, one wave per list, and one [G, cap, 2] int32 scratch buffer; nothing synchronises
     and everything is graph-capturable."""
     G, n, cap, dev, row_, val_ = _lists(col_ptr, row, val)
-    waves = _waves(waves)
+    waves = check_waves(waves, 4)
     if out is None:
         vrow = torch.zeros(G, cap, device=dev, dtype=torch.int32)
         vval = torch.zeros(G, cap, device=dev, dtype=torch.float32)
@@ -89,24 +79,18 @@ def list_auroc(col_ptr: torch.Tensor, vrow: torch.Tensor, vval: torch.Tensor, fl
     ``out``: the two buffers to fill, every slot is written.  One launch, one wave per list; nothing
     synchronises."""
     G, n, cap, dev, row_, val_ = _lists(col_ptr, vrow, vval)
-    K, waves = check_concepts(n_concepts), _waves(waves)
+    K, waves = check_concepts(n_concepts), check_waves(waves, 4)
     if flags.dim() != 1 or flags.shape[0] < 1:
         raise ValueError("flags must be int32 [N] with N >= 1")
     N = flags.shape[0]
     _buffer("flags", flags, torch.int32, (N,), dev)
     if N > INT32_MAX or cap > INT32_MAX:
         raise ValueError(f"list_auroc needs N < 2^31 and cap < 2^31 (got N={N}, cap={cap})")
-    spec = (("pos_in", torch.int32), ("u2", torch.int64))
-    if out is None:
-        out = tuple(torch.empty(G, n, K, device=dev, dtype=dt) for _, dt in spec)
-    if len(out) != 2:
-        raise ValueError("out must hold the 2 buffers ['pos_in', 'u2']")
-    for t, (name, dt) in zip(out, spec):
-        _buffer(f"out {name}", t, dt, (G, n, K), dev)
+    out = out_buffers((("pos_in", torch.int32, (G, n, K)), ("u2", torch.int64, (G, n, K))), out, dev)
     if G == 0:
-        return tuple(out)
+        return out
     ptr = stored_ptr(col_ptr, cap)
     rc = _lib.lib().sc_list_auroc(_lib.ptr(ptr), _lib.ptr(row_), _lib.ptr(val_), _lib.ptr(flags), _lib.ptr(out[0]),
                                   _lib.ptr(out[1]), G, n, cap, N, K, waves, _lib.stream_handle())
     _lib.check(rc, "sc_list_auroc")
-    return tuple(out)
+    return out
