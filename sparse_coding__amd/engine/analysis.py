@@ -1,9 +1,9 @@
 """The analyses on top of ``encode_sparse``, written once for every engine that has sparse codes.
 
 ``CodeAnalyses`` is a mixin: ``interference``, ``recon_profile``, ``feature_examples``, ``coactivation``,
-``label_profile``, ``value_order``, ``feature_auroc``, ``attribution``, ``fvu_top_activating`` and ``atom_matches``
-are each one composition of ``encode_sparse`` with the route of its module (``engine/interference.py`` ..
-``engine/atom_match.py``).  A
+``label_profile``, ``value_order``, ``feature_auroc``, ``ridge_probes``, ``attribution``, ``fvu_top_activating``
+and ``atom_matches`` are each one composition of ``encode_sparse`` with the route of its module
+(``engine/interference.py`` .. ``engine/atom_match.py``).  A
 provider keeps what really differs between engines:
 
 * ``encode_sparse(rows, *, budget=None)`` and ``feature_stats(rows, ...)``: its own loops over the pool;
@@ -226,6 +226,33 @@ class CodeAnalyses:
         self._analysis_refusal("feature_auroc")
         codes = self.encode_sparse(rows, budget=budget)
         return vo.feature_auroc(codes, flags, n_concepts, self._live_counts(), kernels=self._kernels)
+
+    @torch.no_grad()
+    def ridge_probes(self, rows: torch.Tensor, flags: torch.Tensor, *, n_concepts: Optional[int] = None,
+                     alpha: float = 1.0, fit_rows: Optional[torch.Tensor] = None, max_iter: int = 64,
+                     tol: float = 1e-5, budget: Optional[int] = None):
+        """Is each of up to 32 concepts linearly readable from the code of every model as a whole on ``rows``
+        [N, d] (N a positive multiple of the batch size), and which features carry it: an
+        ``engine.probe.LinearProbes`` -- exactly ``RidgeClassifier(alpha)`` per (model, concept), the reference's
+        whole-dictionary probe (``ridge_regression_auroc``) for the whole ensemble -- with ``weight`` [G, n, K],
+        ``intercept``, ``auroc()`` / ``auroc_heldout()`` (exact, ties counting half), ``auroc_predicted()`` (the
+        reference's number) and ``top_features(m)``.  ``flags``: int32 words [N], bit k set where the row is a
+        positive of concept k (``n_concepts`` of them, default 32), or a bool [N, K] matrix.  ``fit_rows``: bool
+        [N], the rows the fit sees (default all); the others are held out and only scored.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, the transposition, then CGLS for all
+        models and concepts in lockstep: per iteration one product over the CSR rows and one over the feature
+        lists, 32 right-hand sides each, with fp64 sums (``csrc/probe.hip``); no dense codes, and the loop reads
+        nothing to the host.  The codes must be complete: a ``budget`` that is too small raises
+        ``SparseCodesOverflow``.  Masked ensembles: features at or past ``dict_size[g]`` have weight 0.  There is
+        no ``state=``.  Parameters, moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and
+        captured graphs are left as they are."""
+        from . import probe as pb
+
+        self._analysis_refusal("ridge_probes")
+        codes = self.encode_sparse(rows, budget=budget)
+        return pb.ridge_probes(codes, flags, n_concepts, alpha=alpha, fit_rows=fit_rows, max_iter=max_iter, tol=tol,
+                               nactive=self._live_counts(), kernels=self._kernels)
 
     @torch.no_grad()
     def attribution(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None,

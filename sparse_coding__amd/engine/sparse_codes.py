@@ -128,6 +128,17 @@ class SparseCodes:
 
         return co.coactivation(self, other, **kw)
 
+    def ridge_probes(self, flags: torch.Tensor, n_concepts=None, **kw):
+        """Ridge probes on the whole code of every model for up to 32 concepts at once, an
+        ``engine.probe.LinearProbes``: exactly ``RidgeClassifier(alpha)`` per (model, concept) -- weights,
+        intercept, and the exact AUROC of the scores over the fit rows and the held-out rows.  ``flags``: int32
+        words [n_rows] (bit k: the row is a positive of concept k) or a bool [n_rows, K] matrix (keywords
+        ``alpha``, ``fit_rows``, ``max_iter``, ``tol``, ``nactive`` of ``engine.probe.ridge_probes``).  The kernels
+        of ``csrc/probe.hip`` when the tensors are on a GPU, the torch oracle elsewhere."""
+        from . import probe as pb
+
+        return pb.ridge_probes(self, flags, n_concepts, **kw)
+
     def to_torch_csr(self, g: int) -> torch.Tensor:
         """Model ``g`` as a ``torch.sparse_csr_tensor`` [n_rows, n] (fp32 values, int64 indices)."""
         self.check()

@@ -389,6 +389,13 @@ class EnsembleTrainer:
         ``n_concepts``, ``budget``); routed by ``_analyses``."""
         return self._analyses("feature_auroc").feature_auroc(rows.to(self.device), flags.to(self.device), **kw)
 
+    def ridge_probes(self, rows: torch.Tensor, flags: torch.Tensor, **kw):
+        """``CodeAnalyses.ridge_probes`` of the engine (``flags`` int32 words [N] or bool [N, K]; keywords
+        ``n_concepts``, ``alpha``, ``fit_rows``, ``max_iter``, ``tol``, ``budget``); routed by ``_analyses``."""
+        if kw.get("fit_rows") is not None:
+            kw["fit_rows"] = kw["fit_rows"].to(self.device)
+        return self._analyses("ridge_probes").ridge_probes(rows.to(self.device), flags.to(self.device), **kw)
+
     def attribution(self, rows: torch.Tensor, **kw):
         """``CodeAnalyses.attribution`` of the engine (keywords ``budget``, ``state``, ``return_proj``); routed by
         ``_analyses``."""

@@ -457,6 +457,31 @@ def ridge_regression_auroc(activations: torch.Tensor, labels: torch.Tensor, **kw
     return float(skm.roc_auc_score(y, clf.predict(X)))
 
 
+def ridge_probe_auroc(sparse_codes, flags: torch.Tensor, nactive=None, n_concepts=None, **kw) -> torch.Tensor:
+    """fp64 [G, K]: the exact AUROC, ties counting half, of a ridge probe on the whole code of every model for each
+    of K <= 32 concepts, over the rows the probe was fitted on, from the complete sparse codes of a pool
+    (``engine.sparse_codes.SparseCodes``).  ``flags``: int32 words [n_rows] whose bit k marks the positives of
+    concept k (``n_concepts`` of them, default 32), or a bool [n_rows, K] matrix; ``kw``: ``alpha``, ``fit_rows``,
+    ``max_iter``, ``tol``.  A concept with no positive or no negative reads NaN.  The whole-dictionary counterpart
+    of ``feature_auroc``.  From ``engine.probe.ridge_probes``: the kernels of ``csrc/probe.hip`` on a GPU, the torch
+    oracle elsewhere; its ``LinearProbes`` also holds the weights and the held-out AUROC."""
+    from ..engine.probe import ridge_probes
+
+    return ridge_probes(sparse_codes, flags, n_concepts, nactive=nactive, **kw).auroc()
+
+
+def ensemble_ridge_regression_auroc(engine, activations: torch.Tensor, labels: torch.Tensor, **kw) -> torch.Tensor:
+    """``ridge_regression_auroc`` for a whole ensemble, on the device: fp64 [G] (``labels`` [N], one concept) or
+    [G, K] (``labels`` [N, K]) -- the AUROC of the hard predictions of ``RidgeClassifier(alpha)`` fitted on the
+    codes of every model of ``engine`` (a fused engine or an ``EnsembleTrainer``) on ``activations`` [N, d], which
+    is their balanced accuracy (reference :252-258 scores ``clf.predict``).  ``labels``: bool, or numbers with
+    positives > 0.  ``kw``: ``alpha``, ``max_iter``, ``tol``, ``budget``."""
+    labels = labels if labels.dtype == torch.bool else labels > 0
+    one = labels.dim() == 1
+    out = engine.ridge_probes(activations, labels.unsqueeze(1) if one else labels, **kw).auroc_predicted()
+    return out[:, 0] if one else out
+
+
 def cluster_vectors(learned_dict: LearnedDict, n_clusters: int = 100, top_clusters: int = 10,
                     seed: int = 0) -> List[List[int]]:
     """K-means over dictionary atoms; returns the feature indices of the largest clusters

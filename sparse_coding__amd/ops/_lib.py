@@ -99,6 +99,12 @@ def signatures():
                                   c_long, c_int, c_void_p],
         "sc_list_auroc": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_long,
                           c_int, c_int, c_void_p],
+        "sc_probe_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_int, c_long, c_int, c_long, c_int, c_void_p],
+        "sc_probe_lists": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                           c_int, c_long, c_long, c_long, c_long, c_int, c_void_p],
+        "sc_probe_dots": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p],
+        "sc_probe_axpby": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
