@@ -1,8 +1,8 @@
 """The analyses on top of ``encode_sparse``, written once for every engine that has sparse codes.
 
 ``CodeAnalyses`` is a mixin: ``interference``, ``recon_profile``, ``feature_examples``, ``coactivation``,
-``label_profile``, ``value_order``, ``feature_auroc``, ``ridge_probes``, ``attribution``, ``fvu_top_activating``
-and ``atom_matches`` are each one composition of ``encode_sparse`` with the route of its module
+``label_profile``, ``value_order``, ``feature_auroc``, ``ridge_probes``, ``logistic_probes``, ``attribution``,
+``fvu_top_activating`` and ``atom_matches`` are each one composition of ``encode_sparse`` with the route of its module
 (``engine/interference.py`` .. ``engine/atom_match.py``).  A
 provider keeps what really differs between engines:
 
@@ -253,6 +253,35 @@ class CodeAnalyses:
         codes = self.encode_sparse(rows, budget=budget)
         return pb.ridge_probes(codes, flags, n_concepts, alpha=alpha, fit_rows=fit_rows, max_iter=max_iter, tol=tol,
                                nactive=self._live_counts(), kernels=self._kernels)
+
+    @torch.no_grad()
+    def logistic_probes(self, rows: torch.Tensor, flags: torch.Tensor, *, n_concepts: Optional[int] = None,
+                        C: float = 1.0, fit_rows: Optional[torch.Tensor] = None, max_iter: int = 12,
+                        cg_iter: int = 16, tol: float = 1e-4, early_stop: bool = True,
+                        budget: Optional[int] = None):
+        """The logistic counterpart of ``ridge_probes`` on ``rows`` [N, d] (N a positive multiple of the batch
+        size): an ``engine.probe.LogisticProbes`` -- exactly ``LogisticRegression(C=C)`` per (model, concept), the
+        reference's ``logistic_regression_auroc`` for the whole ensemble -- with ``weight`` [G, n, K],
+        ``intercept``, ``auroc()`` / ``auroc_heldout()`` (of the logits: the AUROC of ``predict_proba``, exact),
+        ``auroc_predicted()``, ``predict_proba(codes)`` and ``top_features(m)``.  ``flags`` and ``fit_rows`` as in
+        ``ridge_probes``.
+
+        ``encode_sparse(rows, budget=budget)`` under its budget contract, the transposition, then truncated
+        Newton-CG for all models and concepts in lockstep: ``max_iter`` outer steps of ``cg_iter`` Hessian
+        products each, every product one pass over the CSR rows and one over the feature lists with fp64 sums,
+        and a line search over eight step candidates in one pass (``csrc/probe.hip``); no dense codes.  With
+        ``early_stop`` the loop reads one bool per outer step to the host, without it nothing; the result is the
+        same.  The codes must be complete: a ``budget`` that is too small raises ``SparseCodesOverflow``.  Masked
+        ensembles: features at or past ``dict_size[g]`` have weight 0.  There is no ``state=``.  Parameters,
+        moments, shadows, ``feature_counts``, ``rows_seen``, the step counter and captured graphs are left as they
+        are."""
+        from . import probe as pb
+
+        self._analysis_refusal("logistic_probes")
+        codes = self.encode_sparse(rows, budget=budget)
+        return pb.logistic_probes(codes, flags, n_concepts, C=C, fit_rows=fit_rows, max_iter=max_iter,
+                                  cg_iter=cg_iter, tol=tol, early_stop=early_stop, nactive=self._live_counts(),
+                                  kernels=self._kernels)
 
     @torch.no_grad()
     def attribution(self, rows: torch.Tensor, *, budget: Optional[int] = None, state=None,

@@ -27,10 +27,42 @@ the reference's ``ridge_regression_auroc`` and the whole-dictionary counterpart 
   question); ``LinearProbes.scores`` on other codes gives a row that fails it the score 0.
 - **AUROC**: the scores ``C w + b`` of every row, ranked exactly with integer arithmetic (``score_auroc``: ties are
   equal fp32 values and count half), separately over the fit rows and the held-out rows.
+
+``logistic_probes`` fits, on the same codes, rows and concepts, exactly ``sklearn.linear_model.LogisticRegression(C)``:
+``min sum_fit l(z_i, t_i) + |w|^2 / 2C`` with ``z = Xc w + b'``, targets ``t`` in {0, 1}, ``l(z, t) = softplus(z) -
+t z`` and the stable ``softplus(z) = max(z, 0) + log1p(exp(-|z|))``; the intercept is unpenalised and reported as
+``b' - mu . w`` in fp64.  It is the ensemble form of the reference's ``logistic_regression_auroc``.
+
+- **Solver**: truncated Newton-CG in the centred parametrisation, all G models and K concepts in lockstep, written
+  once (``_newton_cg``) for the kernel operator and a dense one.  Vectors are pairs (weights, intercept); per (g, k)::
+
+      w = 0; b' = log(pos / neg); p = sigma(z); r = p - t, D = p (1 - p) on the fit rows, 0 elsewhere
+      g = (Xc^T r + w / C, sum r); g0 = g; f = sum_fit l + |w|^2 / 2C; live = |g0| > 0
+      repeat max_iter times:
+          live &= |g| > tol |g0|;  iters += live                 (early_stop: leave when no (g, k) is live)
+          d = 0; res = p = live ? -g : 0; rho = |res|^2; eta = min(0.5, sqrt(|g| / |g0|)); cgl = live
+          repeat cg_iter times:                                  CG on H d = -g
+              cgl &= rho > eta^2 |g|^2
+              q = D o (Xc p_w + p_b);  h = (Xc^T q + p_w / C, sum q);  a = (cgl and p.h > 0) ? rho / p.h : 0
+              d += a p;  res -= a h;  rho' = |res|^2;  beta = cgl ? rho' / rho : 0
+              p = cgl ? res + beta p : p;  rho = cgl ? rho' : rho;  cg_iters += cgl
+          u = Xc d_w + d_b;  f_j = sum_fit l(z + 2^-j u) + |w + 2^-j d_w|^2 / 2C,  j = 0 .. 7, from one pass
+          s = the largest 2^-j with f_j <= f + 1e-4 2^-j g.d;  none: s = 0, stalled, live = false
+          w += s d_w;  b' += s d_b;  z, r, D, f, g afresh
+      converged = |g| <= tol |g0|
+
+  A finished (or stalled) concept is frozen -- its step is 0 -- so the result is the same for every ``max_iter``
+  past its stop, and the same with and without ``early_stop``, which reads one bool per outer step to the host.
+- **Constant concepts** (no positive or no negative among the fit rows): the maximiser is at infinity; the probes
+  report weight 0 and the intercept ``+-log(2 n_fit)``, the logit at which the absent class has probability
+  ``1 / (2 n_fit + 1)`` -- less than half a row's worth over the fit rows -- ``converged``, and NaN AUROC.
+- **AUROC**: of the logits; sigma is monotone, so it is the reference's ``roc_auc_score(y, predict_proba[:, 1])``
+  without the ties that fp32 probabilities saturate into.
 """
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -504,3 +536,430 @@ def ridge_probes(sparse_codes: SparseCodes, flags: torch.Tensor, n_concepts=None
     res = ridge_probes_reference(sparse_codes, flags, n_concepts, **kw)
     res.weight = res.weight.float()
     return res
+
+
+# ====================================================================== logistic probes
+MIN_TOL_LOGISTIC = 1e-5   # fp32 iterates cannot promise a smaller relative gradient
+ARMIJO = 1e-4             # sufficient-decrease constant of the line search
+
+
+def check_logistic(C, max_iter, cg_iter, tol, min_tol: float = MIN_TOL_LOGISTIC):
+    C = float(C)
+    if not C > 0.0 or not math.isfinite(C):
+        raise ValueError(f"C must be a finite number > 0 (the inverse of the penalty's strength), got {C!r}")
+    for name, v in (("max_iter", max_iter), ("cg_iter", cg_iter)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+    tol = float(tol)
+    if not tol >= min_tol or not tol < 1.0:
+        raise ValueError(f"tol must lie in [{min_tol:g}, 1): fp32 iterates cannot promise less (got {tol!r})")
+    return C, int(max_iter), int(cg_iter), tol
+
+
+def _softplus_loss(z, t):
+    """``softplus(z) - t z`` with the stable ``softplus(z) = max(z, 0) + log1p(exp(-|z|))``; ``t`` bool."""
+    return z.clamp(min=0) + torch.log1p(torch.exp(-z.abs())) - torch.where(t, z, torch.zeros_like(z))
+
+
+def _logit_terms(z, t, m):
+    """(r, D, loss [G, K]) of the margins ``z`` [G, N, K] in their own format: ``t`` bool [N, K] the targets, ``m``
+    bool [N] the fit rows.  From ``e = exp(-|z|)`` alone, as ``csrc/probe.hip``: ``sigma(|z|) = 1 / (1 + e)`` and
+    ``sigma(-|z|) = e / (1 + e)``, so neither sigma nor 1 - sigma is a difference of nearly equal numbers."""
+    e = torch.exp(-z.abs())
+    big = 1.0 / (1.0 + e)
+    small = e * big
+    up = z >= 0
+    r = torch.where(t, -torch.where(up, small, big), torch.where(up, big, small))
+    loss = z.clamp(min=0) + torch.log1p(e) - torch.where(t, z, torch.zeros_like(z))
+    m, zero = m.view(1, -1, 1), torch.zeros_like(z)
+    return torch.where(m, r, zero), torch.where(m, big * small, zero), torch.where(m, loss, zero).sum(1)
+
+
+def logit_terms_reference(Z: torch.Tensor, flags: torch.Tensor, mask: torch.Tensor):
+    """fp64 oracle of ``ops.probe.logit_terms``: ``(R fp64 [G, N, 32], D fp64 [G, N, 32], loss fp64 [G, 32])`` before
+    the one rounding of ``R`` and ``D`` (the summation order of ``loss`` is torch's)."""
+    return _logit_terms(Z.double(), concept_bits(flags, Z.shape[2]), mask != 0)
+
+
+def line_losses_reference(Z: torch.Tensor, U: torch.Tensor, flags: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """fp64 oracle of ``ops.probe.line_losses``: fp64 [G, 8, 32], the loss sums at ``Z + 2^-j U``."""
+    from ..ops.probe import LINE_STEPS
+
+    t, m = concept_bits(flags, Z.shape[2]), (mask != 0).view(1, -1, 1)
+    z, u = Z.double(), U.double()
+    return torch.stack([torch.where(m, _softplus_loss(z + 2.0 ** -j * u, t), torch.zeros_like(z)).sum(1)
+                        for j in range(LINE_STEPS)], 1)
+
+
+@dataclass
+class LogisticProbes:
+    """Logistic-regression probes of G models for K concepts, fitted on the fit rows of a pool of ``n_rows`` rows:
+    exactly ``sklearn.linear_model.LogisticRegression(C=C)`` per (model, concept)."""
+
+    weight: torch.Tensor       # fp32 [G, n, K]
+    intercept: torch.Tensor    # fp64 [G, K]
+    iters: torch.Tensor        # int32 [G, K]  outer (Newton) steps the concept was live
+    cg_iters: torch.Tensor     # int32 [G, K]  inner (CG) iterations the concept was live, in total
+    converged: torch.Tensor    # bool [G, K]
+    stalled: torch.Tensor      # bool [G, K]   no candidate of the line search passed: frozen where it stood
+    resid: torch.Tensor        # fp64 [G, K]   |g| / |g0| at the stop (0 for a constant concept)
+    loss: torch.Tensor         # fp64 [G, K]   the objective at the stop
+    u2_fit: torch.Tensor       # int64 [G, K]  rank sums of the logits over the fit rows (``score_auroc``)
+    pos_fit: torch.Tensor      # int64 [K]
+    cnt_fit: torch.Tensor      # int64 []
+    tp_fit: torch.Tensor       # int64 [G, K]  positives of the fit rows with logit > 0
+    tn_fit: torch.Tensor       # int64 [G, K]  negatives of the fit rows without
+    u2_held: torch.Tensor      # the same over the held-out rows
+    pos_held: torch.Tensor
+    cnt_held: torch.Tensor
+    tp_held: torch.Tensor
+    tn_held: torch.Tensor
+    skipped: torch.Tensor      # int64 [G]     rows the scoring pass left out by the skip rule (a fit refuses them)
+    C: float
+    n_rows: int
+
+    _TENSORS = ("weight", "intercept", "iters", "cg_iters", "converged", "stalled", "resid", "loss", "u2_fit",
+                "pos_fit", "cnt_fit", "tp_fit", "tn_fit", "u2_held", "pos_held", "cnt_held", "tp_held", "tn_held",
+                "skipped")
+
+    n_concepts = LinearProbes.n_concepts
+    _ratio = staticmethod(LinearProbes._ratio)
+    top_features = LinearProbes.top_features
+
+    def auroc(self) -> torch.Tensor:
+        """fp64 [G, K]: the exact AUROC of the **logits** over the fit rows, ties counting half; NaN for a concept
+        with no positive or no negative among them.  Sigma is monotone, so this is the reference's
+        ``roc_auc_score(y, clf.predict_proba(X)[:, 1])`` -- without the ties that fp32 probabilities saturate
+        into at 0 and 1."""
+        return self._ratio(self.u2_fit, self.pos_fit, self.cnt_fit)
+
+    def auroc_heldout(self) -> torch.Tensor:
+        """fp64 [G, K]: the same over the held-out rows (NaN everywhere when no row was held out)."""
+        return self._ratio(self.u2_held, self.pos_held, self.cnt_held)
+
+    def auroc_predicted(self, heldout: bool = False) -> torch.Tensor:
+        """fp64 [G, K]: the AUROC of the hard predictions ``logit > 0`` (probability above one half), which is
+        their balanced accuracy.  From integer counts; NaN for a concept with no positive or no negative."""
+        return LinearProbes.auroc_predicted(self, heldout)
+
+    def scores(self, sparse_codes: SparseCodes, nactive=None, *, kernels: Optional[bool] = None) -> torch.Tensor:
+        """fp32 [G, N', K]: the logits ``C w + b`` on any codes of the same models (``ops.probe.rows_matmul`` when
+        they are on a GPU, dense torch elsewhere or with ``kernels=False``).  A row the skip rule leaves out
+        scores 0."""
+        return LinearProbes.scores(self, sparse_codes, nactive, kernels=kernels)
+
+    def predict_proba(self, sparse_codes: SparseCodes, nactive=None, *, kernels: Optional[bool] = None):
+        """fp32 [G, N', K]: ``sigma(scores)``, the probability of the positive class (torch)."""
+        return torch.sigmoid(self.scores(sparse_codes, nactive, kernels=kernels))
+
+    def state_dict(self):
+        sd = {k: getattr(self, k) for k in self._TENSORS}
+        sd["C"] = torch.tensor(float(self.C), dtype=torch.float64)
+        sd["n_rows"] = torch.tensor(int(self.n_rows), dtype=torch.int64)
+        return sd
+
+    def save(self, path):
+        torch.save({k: v.detach().cpu() for k, v in self.state_dict().items()}, path)
+
+    @classmethod
+    def load(cls, path, map_location="cpu") -> "LogisticProbes":
+        sd = torch.load(path, map_location=map_location, weights_only=True)
+        return cls(*(sd[k] for k in cls._TENSORS), float(sd["C"]), int(sd["n_rows"]))
+
+    def to(self, device) -> "LogisticProbes":
+        return LogisticProbes(*(getattr(self, k).to(device) for k in self._TENSORS), self.C, self.n_rows)
+
+
+# ---------------------------------------------------------------------- the operators of the Newton loop
+class _DenseLogitOps(_DenseOps):
+    """``_DenseOps`` with the logistic terms: every product, sum and scalar in ``dtype``."""
+
+    def __init__(self, dense, mask, dtype, bits):
+        super().__init__(dense, mask, dtype)
+        self.t, self.fit, self.n_models = bits, mask, dense.shape[0]
+        self.vdtype = self.sdtype = dtype
+
+    def margins(self, v, vb, slot="z"):     # Xc v + vb on the fit rows
+        return self.forward(v) + vb.unsqueeze(1) * self.m
+
+    def terms(self, z):
+        return _logit_terms(z, self.t, self.fit)
+
+    def grad(self, r, w, lam):              # (Xc^T r + lam w, sum r)
+        return self.adjoint(r, w, -lam), r.sum(1)
+
+    def hess(self, D, v, vb, lam):          # the same of q = D o (Xc v + vb)
+        return self.grad(D * self.margins(v, vb), v, lam)
+
+    def line(self, z, u):
+        from ..ops.probe import LINE_STEPS
+
+        m, zero = self.fit.view(1, -1, 1), torch.zeros_like(z)
+        return torch.stack([torch.where(m, _softplus_loss(z + 2.0 ** -j * u, self.t), zero).sum(1)
+                            for j in range(LINE_STEPS)], 1)
+
+
+class _KernelLogitOps(_KernelOps):
+    """``_KernelOps`` with the logistic kernels: fp32 iterates [G, M, 32], fp64 sums and scalars [G, 32]."""
+
+    vdtype, sdtype = torch.float32, torch.float64
+
+    def __init__(self, sc, fc, fit, nactive, waves, flags):
+        super().__init__(sc, fc, fit, nactive, waves)
+        G, N, dev = sc.n_models, sc.n_rows, sc.col.device
+        self.flags, self.n_models = flags.contiguous(), G
+        self.slots = {k: torch.empty(G, N, CONCEPTS, device=dev, dtype=torch.float32) for k in ("z", "u", "r", "D")}
+        self.loss = torch.empty(G, CONCEPTS, device=dev, dtype=torch.float64)
+
+    def _rows(self, v, vb, out, scale=None):
+        shift = self.pr.col_dots(v, self.mu32, waves=self.waves) - vb
+        self.pr.rows_matmul(self.row_ptr, self.sc.col, self.sc.val, v, shift=shift, mask=self.mask,
+                            nactive=self.nactive, skipped=self.scratch, out=out, waves=self.waves, scale=scale)
+        return out
+
+    def margins(self, v, vb, slot="z"):
+        return self._rows(v, vb, self.slots[slot])
+
+    def terms(self, z):
+        return self.pr.logit_terms(z, self.flags, self.mask, out=(self.slots["r"], self.slots["D"], self.loss),
+                                   waves=self.waves)
+
+    def grad(self, r, w, lam):
+        S, su = self.lists(r), self.pr.col_dots(r, waves=self.waves)
+        return (S.double() - self.mu64 * su.unsqueeze(1) + lam * w.double()).float(), su
+
+    def hess(self, D, v, vb, lam):
+        return self.grad(self._rows(v, vb, self.q, scale=D), v, lam)
+
+    def line(self, z, u):
+        return self.pr.line_losses(z, u, self.flags, self.mask, waves=self.waves)
+
+
+def _armijo(fj, f, gd, steps):
+    """(step [G, C], found bool [G, C]): the largest candidate ``steps[j]`` with ``fj[:, j] <= f + ARMIJO steps[j]
+    gd`` (``fj`` [G, J, C] the objective at the candidates, ``f`` at 0, ``gd`` the slope)."""
+    step = torch.zeros_like(f)
+    for j in reversed(range(steps.numel())):
+        step = torch.where(fj[:, j] <= f + ARMIJO * steps[j] * gd, steps[j], step)
+    return step, step > 0
+
+
+def _newton_cg(ops, n: int, pos, C: float, max_iter: int, cg_iter: int, tol: float, early_stop: bool = True,
+               step_rule=_armijo):
+    """The recurrence of the module docstring on ``ops``; ``pos`` [C] the positives among the fit rows.  Returns
+    (w, b', iters, cg_iters, converged, stalled, resid, objective); every scalar is [G, C] in ``ops``' format."""
+    from ..ops.probe import LINE_STEPS
+
+    sd, dev, G, cols = ops.sdtype, pos.device, ops.n_models, pos.numel()
+    lam = 1.0 / C
+    nfit = ops.nfit.to(sd)
+    pos = pos.to(sd)
+    neg = nfit - pos
+    const = (pos == 0) | (neg == 0)
+    clip = torch.log(2 * nfit)
+    one, zero = torch.ones(G, cols, dtype=sd, device=dev), torch.zeros(G, cols, dtype=sd, device=dev)
+    b0 = torch.where(const, torch.where(pos > 0, clip, -clip),
+                     torch.log(torch.where(const, one[0], pos) / torch.where(const, one[0], neg)))
+    b = b0.expand(G, cols).clone()
+    w = torch.zeros(G, n, cols, dtype=ops.vdtype, device=dev)
+    d, res, p = torch.zeros_like(w), torch.zeros_like(w), torch.zeros_like(w)
+
+    def evaluate():
+        z = ops.margins(w, b)
+        r, D, L = ops.terms(z)
+        ww = ops.dots(w, w)
+        gw, gb = ops.grad(r, w, lam)
+        return z, D, ww, L + 0.5 * lam * ww, gw, gb, ops.dots(gw, gw) + gb * gb
+
+    z, D, ww, f, gw, gb, gn2 = evaluate()
+    g0 = gn2.clone()
+    live = ~const & (g0 > 0)
+    stalled = torch.zeros_like(live)
+    iters = torch.zeros(G, cols, dtype=torch.int32, device=dev)
+    cg_iters = torch.zeros_like(iters)
+    tol2 = ops.scalar(torch.tensor(tol, dtype=torch.float64)) ** 2
+    steps = (2.0 ** -torch.arange(LINE_STEPS, dtype=torch.float64, device=dev)).to(sd)
+    for _ in range(max_iter):
+        live = live & (gn2 > tol2 * g0)
+        if early_stop and not bool(live.any()):
+            break
+        iters += live.to(torch.int32)
+        # conjugate gradients on H d = -g, truncated at |res| <= eta |g|
+        lv = torch.where(live, one, zero)
+        d.zero_()
+        db = zero.clone()
+        ops.axpby_(res, gw, -lv, zero)
+        rb = -gb * lv
+        ops.axpby_(p, res, one, zero)
+        pb = rb.clone()
+        rho = gn2 * lv
+        stop2 = torch.minimum(0.25 * one, torch.sqrt(gn2 / torch.where(g0 > 0, g0, one))) * gn2
+        cgl = live
+        for _ in range(cg_iter):
+            cgl = cgl & (rho > stop2)
+            hw, hb = ops.hess(D, p, pb, lam)
+            php = ops.dots(p, hw) + pb * hb
+            ok = cgl & (php > 0)
+            a = torch.where(ok, rho / torch.where(ok, php, one), zero)
+            ops.axpby_(d, p, a, one)
+            db = db + a * pb
+            ops.axpby_(res, hw, -a, one)
+            rb = rb - a * hb
+            rho_new = ops.dots(res, res) + rb * rb
+            beta = torch.where(cgl, rho_new / torch.where(cgl, rho, one), zero)
+            ops.axpby_(p, res, torch.where(cgl, one, zero), torch.where(cgl, beta, one))
+            pb = torch.where(cgl, rb + beta * pb, pb)
+            rho = torch.where(cgl, rho_new, rho)
+            cg_iters += cgl.to(torch.int32)
+        # Armijo backtracking over the candidates 2^-j, all from one pass: z is linear in the step
+        u = ops.margins(d, db, "u")
+        gd = ops.dots(gw, d) + gb * db
+        wd, dd = ops.dots(w, d), ops.dots(d, d)
+        t = steps.view(1, -1, 1)
+        fj = ops.line(z, u) + 0.5 * lam * (ww.unsqueeze(1) + 2 * t * wd.unsqueeze(1) + t * t * dd.unsqueeze(1))
+        step, found = step_rule(fj, f, gd, steps)
+        stalled = stalled | (live & ~found)
+        live = live & found
+        step = torch.where(live, step, zero)
+        ops.axpby_(w, d, step, one)
+        b = b + step * db
+        z, D, ww, f, gw, gb, gn2 = evaluate()
+    converged = const | (gn2 <= tol2 * g0)
+    resid = torch.where(const, zero, torch.sqrt(gn2 / torch.where(g0 > 0, g0, one)))
+    return w, b, iters, cg_iters, converged, stalled, resid.double(), f.double()
+
+
+def _finish_logistic(w, b, out, scores, skipped, bits, fit, C, n_rows) -> LogisticProbes:
+    it, cg, conv, stalled, resid, loss = out
+    fit_sums = score_auroc(scores, bits, fit)
+    held_sums = score_auroc(scores, bits, ~fit)
+    return LogisticProbes(w, b, it, cg, conv, stalled, resid, loss, *fit_sums, *held_sums, skipped, float(C),
+                          int(n_rows))
+
+
+def logistic_probes_reference(sparse_codes: SparseCodes, flags: torch.Tensor, n_concepts=None, *, C: float = 1.0,
+                              fit_rows=None, max_iter: int = 12, cg_iter: int = 16, tol: float = 1e-4,
+                              early_stop: bool = True, nactive=None, dtype=torch.float64) -> LogisticProbes:
+    """Torch oracle of ``logistic_probes`` (any device; this is what runs off the GPU): the same recurrence on
+    ``to_dense`` codes with every product, sum and scalar in ``dtype`` -- fp64 is the reference (its ``weight`` is
+    fp64, and ``tol`` may go below the device route's floor), fp32 the plain evaluation of the recurrence that the
+    device route's error is measured against."""
+    C, max_iter, cg_iter, tol = check_logistic(C, max_iter, cg_iter, tol,
+                                               1e-15 if dtype == torch.float64 else MIN_TOL_LOGISTIC)
+    sparse_codes.check()
+    dev = sparse_codes.col.device
+    flags, K = check_flags(flags, sparse_codes.n_rows, n_concepts, dev)
+    fit = check_fit_rows(fit_rows, sparse_codes.n_rows, dev)
+    bits = concept_bits(flags, K)
+    dense, bad = _dense_codes(sparse_codes, nactive, dtype)
+    if bool(bad.any()):
+        raise FeatureCodesSkipped(f"{bad.sum(1).tolist()} rows per model fail the skip rule (of "
+                                  f"{sparse_codes.n_rows}): logistic_probes needs valid codes for every row")
+    ops = _DenseLogitOps(dense, fit, dtype, bits)
+    w, bc, *out = _newton_cg(ops, sparse_codes.n, (bits & fit.unsqueeze(1)).sum(0), C, max_iter, cg_iter, tol,
+                             early_stop)
+    b = (bc - ops.mu_dot(w)).double()
+    scores = _scores_dense(dense.double(), bad, w.double(), b).float()
+    return _finish_logistic(w, b, out, scores, bad.sum(1), bits, fit, C, sparse_codes.n_rows)
+
+
+def logistic_probes_fused(sparse_codes: SparseCodes, flags: torch.Tensor, n_concepts=None, *, C: float = 1.0,
+                          fit_rows=None, max_iter: int = 12, cg_iter: int = 16, tol: float = 1e-4,
+                          early_stop: bool = True, nactive=None, feature_codes=None,
+                          waves: Optional[int] = None) -> LogisticProbes:
+    """``logistic_probes`` on the kernels of ``csrc/probe.hip``: ``by_feature`` (or ``feature_codes``), then per
+    outer step one ``logit_terms``, per inner iteration one ``rows_matmul(scale=D)`` over the CSR rows and one
+    ``lists_matmul`` over the feature lists, and one ``line_losses`` for the eight step candidates; the logits are
+    one more ``rows_matmul``.  Synchronises before the loop (``SparseCodes.check()`` and ``FeatureCodes.check()``);
+    with ``early_stop`` the loop reads one bool per outer step, without it nothing."""
+    from .feature_codes import by_feature
+    from .value_order import concept_words
+
+    C, max_iter, cg_iter, tol = check_logistic(C, max_iter, cg_iter, tol)
+    sparse_codes.check()
+    dev = sparse_codes.col.device
+    flags, K = check_flags(flags, sparse_codes.n_rows, n_concepts, dev)
+    fit = check_fit_rows(fit_rows, sparse_codes.n_rows, dev)
+    bits = concept_bits(flags, K)
+    nactive = _nactive(nactive, sparse_codes)
+    fc = (by_feature(sparse_codes, nactive) if feature_codes is None else feature_codes).check()
+    ops = _KernelLogitOps(sparse_codes, fc, fit, nactive, waves, concept_words(bits))
+    w, bc, *out = _newton_cg(ops, sparse_codes.n, _pad((bits & fit.unsqueeze(1)).sum(0)), C, max_iter, cg_iter, tol,
+                             early_stop)
+    b = (bc - ops.mu_dot(w))[:, :K].contiguous()
+    w = w[..., :K].contiguous()
+    scores, skipped = _scores_fused(sparse_codes, w, b, nactive, waves)
+    return _finish_logistic(w, b, [t[:, :K].contiguous() for t in out], scores, skipped, bits, fit, C,
+                            sparse_codes.n_rows)
+
+
+def logistic_probes(sparse_codes: SparseCodes, flags: torch.Tensor, n_concepts=None, *,
+                    kernels: Optional[bool] = None, **kw) -> LogisticProbes:
+    """The ``LogisticProbes`` of the complete sparse codes ``sparse_codes`` against the concepts of ``flags`` (int32
+    words [n_rows], ``n_concepts`` of them, default 32, or a bool [n_rows, K] matrix): keywords ``C`` (1.0,
+    sklearn's default), ``fit_rows``, ``max_iter`` (12), ``cg_iter`` (16), ``tol`` (1e-4), ``early_stop``,
+    ``nactive``.  The kernels when the codes are on a GPU (further keywords ``feature_codes``, ``waves``), the oracle
+    elsewhere or with ``kernels=False`` (its fp64 weights rounded to fp32).  The floor of ``tol`` belongs to fp32
+    iterates: the kernels (and the oracle with ``dtype=torch.float32``) refuse a ``tol`` below 1e-5, the fp64 oracle
+    that runs off the GPU takes any ``tol`` down to 1e-15, as in ``ridge_probes``.  Synchronises
+    before the fit (``SparseCodesOverflow`` if entries were dropped, ``FeatureCodesSkipped`` if a row fails the
+    skip rule)."""
+    if sparse_codes.col.is_cuda if kernels is None else kernels:
+        return logistic_probes_fused(sparse_codes, flags, n_concepts, **kw)
+    for k in ("feature_codes", "waves"):
+        if kw.pop(k, None) is not None:
+            raise TypeError(f"logistic_probes: {k} is a keyword of the device route")
+    res = logistic_probes_reference(sparse_codes, flags, n_concepts, **kw)
+    res.weight = res.weight.float()
+    return res
+
+
+def logistic_newton_reference(dense: torch.Tensor, bits: torch.Tensor, C: float = 1.0, fit_rows=None,
+                              max_steps: int = 100):
+    """Plain dense Newton with exact solves, for small n: ``(weight fp64 [G, n, K], intercept fp64 [G, K])`` of
+    ``LogisticRegression(C=C)`` on the rows ``fit_rows`` of the dense codes ``dense`` [G, N, n] with targets from
+    ``bits`` bool [N, K], run until ``|g| <= 1e-12 |g0|`` (g0 the gradient at w = 0, b = log(pos / neg)) or until
+    the objective stops falling in fp64.  A concept that is constant on the rows gets weight 0 and intercept
+    ``+-log(2 n_fit)``, as the probes do."""
+    X = dense.double()
+    if fit_rows is not None:
+        X, bits = X[:, fit_rows], bits[fit_rows]
+    G, N, n = X.shape
+    K = bits.shape[1]
+    t = bits.unsqueeze(0)
+    A = torch.cat([X, torch.ones(G, N, 1, dtype=torch.float64, device=X.device)], 2)            # [G, N, n + 1]
+    pen = torch.full((n + 1,), 1.0 / C, dtype=torch.float64, device=X.device)
+    pen[n] = 0.0
+    pos = bits.sum(0).double()
+    const = (pos == 0) | (pos == N)
+    safe = torch.where(const, torch.ones_like(pos), pos)
+    theta = torch.zeros(G, K, n + 1, dtype=torch.float64, device=X.device)
+    clip = torch.log(torch.tensor(2.0 * N, dtype=torch.float64, device=X.device))
+    theta[..., n] = torch.where(const, torch.where(pos > 0, clip, -clip),
+                                torch.log(safe / torch.where(const, torch.ones_like(pos), N - pos)))
+    every = torch.ones(N, dtype=torch.bool, device=X.device)
+
+    def at(th):
+        r, D, L = _logit_terms(A @ th.transpose(1, 2), bits, every)
+        return r, D, L + 0.5 * (pen * th * th).sum(-1), (A.transpose(1, 2) @ r).transpose(1, 2) + pen * th
+
+    r, D, f, g = at(theta)
+    g0 = g.norm(dim=-1)
+    for _ in range(max_steps):
+        live = ~const & (g.norm(dim=-1) > 1e-12 * g0)
+        if not bool(live.any()):
+            break
+        H = (A.unsqueeze(1) * D.transpose(1, 2).unsqueeze(-1)).transpose(2, 3) @ A.unsqueeze(1) + torch.diag(pen)
+        H = torch.where(live[..., None, None], H, torch.eye(n + 1, dtype=torch.float64, device=X.device))
+        step = torch.linalg.solve(H, -(g * live.unsqueeze(-1)).unsqueeze(-1)).squeeze(-1)
+        slope = (g * step).sum(-1)
+        moved = torch.zeros_like(live)
+        for j in range(40):                                              # backtracking: the first 2^-j that descends
+            cand = theta + 2.0 ** -j * step
+            ok = live & ~moved & (at(cand)[2] <= f + ARMIJO * 2.0 ** -j * slope)
+            theta = torch.where(ok.unsqueeze(-1), cand, theta)
+            moved |= ok
+        if not bool(moved.any()):
+            break
+        r, D, f, g = at(theta)
+    return theta[..., :n].transpose(1, 2).contiguous(), theta[..., n].contiguous()

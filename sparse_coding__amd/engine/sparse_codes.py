@@ -139,6 +139,17 @@ class SparseCodes:
 
         return pb.ridge_probes(self, flags, n_concepts, **kw)
 
+    def logistic_probes(self, flags: torch.Tensor, n_concepts=None, **kw):
+        """Logistic-regression probes on the whole code of every model for up to 32 concepts at once, an
+        ``engine.probe.LogisticProbes``: exactly ``LogisticRegression(C=C)`` per (model, concept) -- weights,
+        intercept, and the exact AUROC of the logits over the fit rows and the held-out rows.  ``flags`` as in
+        ``ridge_probes`` (keywords ``C``, ``fit_rows``, ``max_iter``, ``cg_iter``, ``tol``, ``early_stop``,
+        ``nactive`` of ``engine.probe.logistic_probes``).  The kernels of ``csrc/probe.hip`` when the tensors are
+        on a GPU, the torch oracle elsewhere."""
+        from . import probe as pb
+
+        return pb.logistic_probes(self, flags, n_concepts, **kw)
+
     def to_torch_csr(self, g: int) -> torch.Tensor:
         """Model ``g`` as a ``torch.sparse_csr_tensor`` [n_rows, n] (fp32 values, int64 indices)."""
         self.check()

@@ -396,6 +396,14 @@ class EnsembleTrainer:
             kw["fit_rows"] = kw["fit_rows"].to(self.device)
         return self._analyses("ridge_probes").ridge_probes(rows.to(self.device), flags.to(self.device), **kw)
 
+    def logistic_probes(self, rows: torch.Tensor, flags: torch.Tensor, **kw):
+        """``CodeAnalyses.logistic_probes`` of the engine (``flags`` int32 words [N] or bool [N, K]; keywords
+        ``n_concepts``, ``C``, ``fit_rows``, ``max_iter``, ``cg_iter``, ``tol``, ``early_stop``, ``budget``);
+        routed by ``_analyses``."""
+        if kw.get("fit_rows") is not None:
+            kw["fit_rows"] = kw["fit_rows"].to(self.device)
+        return self._analyses("logistic_probes").logistic_probes(rows.to(self.device), flags.to(self.device), **kw)
+
     def attribution(self, rows: torch.Tensor, **kw):
         """``CodeAnalyses.attribution`` of the engine (keywords ``budget``, ``state``, ``return_proj``); routed by
         ``_analyses``."""

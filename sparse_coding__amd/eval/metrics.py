@@ -482,6 +482,31 @@ def ensemble_ridge_regression_auroc(engine, activations: torch.Tensor, labels: t
     return out[:, 0] if one else out
 
 
+def logistic_probe_auroc(sparse_codes, flags: torch.Tensor, nactive=None, n_concepts=None, **kw) -> torch.Tensor:
+    """fp64 [G, K]: the exact AUROC, ties counting half, of the logits of a logistic-regression probe on the whole
+    code of every model for each of K <= 32 concepts, over the rows the probe was fitted on, from the complete
+    sparse codes of a pool (``engine.sparse_codes.SparseCodes``) -- ``roc_auc_score(y, clf.predict_proba(X)[:, 1])``
+    of ``LogisticRegression(C=C)``, sigma being monotone.  ``flags`` as in ``ridge_probe_auroc``; ``kw``: ``C``,
+    ``fit_rows``, ``max_iter``, ``cg_iter``, ``tol``, ``early_stop``.  From ``engine.probe.logistic_probes``: the
+    kernels of ``csrc/probe.hip`` on a GPU, the torch oracle elsewhere."""
+    from ..engine.probe import logistic_probes
+
+    return logistic_probes(sparse_codes, flags, n_concepts, nactive=nactive, **kw).auroc()
+
+
+def ensemble_logistic_regression_auroc(engine, activations: torch.Tensor, labels: torch.Tensor,
+                                       **kw) -> torch.Tensor:
+    """``logistic_regression_auroc`` for a whole ensemble, on the device: fp64 [G] (``labels`` [N], one concept) or
+    [G, K] (``labels`` [N, K]) -- the AUROC of the predicted probabilities of ``LogisticRegression(C=C)`` fitted
+    on the codes of every model of ``engine`` (a fused engine or an ``EnsembleTrainer``) on ``activations``
+    [N, d], ranked exactly through the logits.  ``labels``: bool, or numbers with positives > 0.  ``kw``: ``C``,
+    ``max_iter``, ``cg_iter``, ``tol``, ``early_stop``, ``budget``."""
+    labels = labels if labels.dtype == torch.bool else labels > 0
+    one = labels.dim() == 1
+    out = engine.logistic_probes(activations, labels.unsqueeze(1) if one else labels, **kw).auroc()
+    return out[:, 0] if one else out
+
+
 def cluster_vectors(learned_dict: LearnedDict, n_clusters: int = 100, top_clusters: int = 10,
                     seed: int = 0) -> List[List[int]]:
     """K-means over dictionary atoms; returns the feature indices of the largest clusters

@@ -105,6 +105,12 @@ def signatures():
                            c_int, c_long, c_long, c_long, c_long, c_int, c_void_p],
         "sc_probe_dots": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p],
         "sc_probe_axpby": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p],
+        "sc_probe_rows_scaled": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_long, c_int, c_long, c_int, c_void_p],
+        "sc_probe_logit": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long,
+                           c_int, c_void_p],
+        "sc_probe_line": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int,
+                          c_void_p],
     }
     optional = {
         "sc_topk_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -24,6 +24,16 @@
 //   probe_axpby_kernel   y[g, m, k] <- a[g, k] x[g, m, k] + b[g, k] y[g, m, k] with fp64 coefficients [G, 32]: the
 //                        vector updates of the iteration, computed in fp64 and rounded once.
 //
+// For logistic probes (the Newton loop of engine/probe.py), on margins Z [G, N, 32] with the targets t = bit k of
+// the flag words int32 [N] and the fit mask w uint8 [N]:
+//   probe_rows_scaled_kernel  Q = D o (C P - 1 (x) c), masked: the body of probe_rows_kernel with one more fp64
+//                        multiply before the rounding (D fp32 [G, N, 32]), so a Hessian product needs no pass of its
+//                        own over [G, N, 32].
+//   probe_logit_kernel   R = sigma(Z) - t, D = sigma(Z) (1 - sigma(Z)) (zeros off the fit rows) and the loss sums
+//                        sum_fit softplus(z) - t z, fp64 [G, 32]: sigma and the loss in fp64 from the fp32 margin,
+//                        rounded once; slabs and fold as probe_dots_kernel.
+//   probe_line_kernel    the loss sums at z + 2^-j u, j = 0 .. 7, fp64 [G, 8, 32]: one read of Z and U.
+//
 // fp64 order, fixed by the code: every lane starts from +0.0 and takes its entries in order with one
 // fma((double)code, (double)operand, acc) each -- even entries (of the row, of the segment, of the slab) in half 0,
 // odd ones in half 1 -- and the result is half 0 + half 1; a fold adds partials in ascending order starting from
@@ -41,6 +51,7 @@ namespace scamd {
 
 constexpr int PROBE_WAVES = 4;     // waves per block, at most
 constexpr int PROBE_SLAB = 1024;   // rows per slab of the dot products (a contract: it fixes the fp64 order)
+constexpr int PROBE_STEPS = 8;     // line-search candidates 2^-j, j = 0 .. 7
 
 // This lane's half of sum_e val[e] T[idx[e], lane & 31] over the entries [lo, hi) (wave-uniform bounds), T [M, 32]
 // with M >= 1: entry lo + 2 i + (lane >> 5) at step i, in order; an entry whose index lies outside [0, M) is left
@@ -72,11 +83,14 @@ __device__ __forceinline__ double probe_join(double acc) { return acc + __shfl_x
 
 __device__ __forceinline__ long probe_uniform(long v) { return (long)__builtin_amdgcn_readfirstlane((int)v); }
 
-__global__ __launch_bounds__(64 * PROBE_WAVES) void probe_rows_kernel(
+// The body of the two row kernels.  SCALED: the row of Q is multiplied by the row of D [G, N, 32] in fp64 before
+// the one rounding; otherwise D is not read.
+template <bool SCALED>
+__device__ __forceinline__ void probe_rows_body(
     const long* __restrict__ row_ptr, const int* __restrict__ col, const float* __restrict__ val, long cap,
     const int* __restrict__ nactive, const float* __restrict__ P, const double* __restrict__ c,
-    const uint8_t* __restrict__ w, int G, int N, int n, int waves, float* __restrict__ Q,
-    unsigned long long* __restrict__ skipped) {
+    const uint8_t* __restrict__ w, const float* __restrict__ D, int G, int N, int n, int waves,
+    float* __restrict__ Q, unsigned long long* __restrict__ skipped) {
   ListWalk lw;
   if (!list_walk(lw, (long)G * N, waves)) return;
   lw.split(N);
@@ -85,6 +99,8 @@ __global__ __launch_bounds__(64 * PROBE_WAVES) void probe_rows_kernel(
   col += (long)g * cap;
   val += (long)g * cap;
   float* q = Q + lw.id * 32;
+  float scale = 1.f;  // (SCALED: loaded before the walk, whose gathers hide its latency; every (g, r) has a row of D)
+  if constexpr (SCALED) scale = D[lw.id * 32 + (lane & 31)];
   if (!csr_row_ok(lo, hi, cap, n, live_limit(nactive, g, n), col, lane)) {
     if (lane < 32) q[lane] = 0.f;
     if (lane == 0) atomicAdd(skipped + g, 1ull);
@@ -98,7 +114,24 @@ __global__ __launch_bounds__(64 * PROBE_WAVES) void probe_rows_kernel(
   hi = probe_uniform(hi);
   double acc = probe_join(probe_walk(col, val, lo, hi, P + (long)g * n * 32, n, lane));
   if (c) acc -= c[g * 32 + (lane & 31)];
+  if constexpr (SCALED) acc *= (double)scale;
   if (lane < 32) q[lane] = (float)acc;
+}
+
+__global__ __launch_bounds__(64 * PROBE_WAVES) void probe_rows_kernel(
+    const long* __restrict__ row_ptr, const int* __restrict__ col, const float* __restrict__ val, long cap,
+    const int* __restrict__ nactive, const float* __restrict__ P, const double* __restrict__ c,
+    const uint8_t* __restrict__ w, int G, int N, int n, int waves, float* __restrict__ Q,
+    unsigned long long* __restrict__ skipped) {
+  probe_rows_body<false>(row_ptr, col, val, cap, nactive, P, c, w, nullptr, G, N, n, waves, Q, skipped);
+}
+
+__global__ __launch_bounds__(64 * PROBE_WAVES) void probe_rows_scaled_kernel(
+    const long* __restrict__ row_ptr, const int* __restrict__ col, const float* __restrict__ val, long cap,
+    const int* __restrict__ nactive, const float* __restrict__ P, const double* __restrict__ c,
+    const uint8_t* __restrict__ w, const float* __restrict__ D, int G, int N, int n, int waves,
+    float* __restrict__ Q, unsigned long long* __restrict__ skipped) {
+  probe_rows_body<true>(row_ptr, col, val, cap, nactive, P, c, w, D, G, N, n, waves, Q, skipped);
 }
 
 __global__ __launch_bounds__(64 * PROBE_WAVES) void probe_lists_kernel(
@@ -181,6 +214,84 @@ __global__ __launch_bounds__(64) void probe_dots_fold_kernel(const double* __res
   out[t] = acc;
 }
 
+// The logistic terms of one margin in fp64, from e = exp(-|z|) alone: sigma(|z|) = 1 / (1 + e) and sigma(-|z|) =
+// e / (1 + e), so neither sigma nor 1 - sigma is a difference of nearly equal numbers, and the loss is the stable
+// softplus max(z, 0) + log1p(e) minus t z.  r = sigma(z) - t, D = sigma(z) (1 - sigma(z)).
+__device__ __forceinline__ double probe_softplus_loss(double z, bool t) {
+  return fmax(z, 0.0) + log1p(exp(-fabs(z))) - (t ? z : 0.0);
+}
+
+__device__ __forceinline__ void probe_logit_terms(double z, bool t, double& r, double& D, double& loss) {
+  const double e = exp(-fabs(z));
+  const double big = 1.0 / (1.0 + e), small = e * big;
+  const bool up = z >= 0.0;
+  r = t ? -(up ? small : big) : (up ? big : small);
+  D = big * small;
+  loss = fmax(z, 0.0) + log1p(e) - (t ? z : 0.0);
+}
+
+// One wave per slab of PROBE_SLAB rows, as probe_dots_kernel: R = sigma(Z) - t and D = sigma (1 - sigma) on the
+// rows with w != 0 (t: bit k of flags[r]), zeros on the others, and the slab's fp64 loss partial.
+__global__ __launch_bounds__(64 * PROBE_WAVES) void probe_logit_kernel(
+    const float* __restrict__ Z, const int* __restrict__ flags, const uint8_t* __restrict__ w, int G, long N,
+    long slabs, int waves, float* __restrict__ R, float* __restrict__ D, double* __restrict__ part) {
+  ListWalk lw;
+  if (!list_walk(lw, (long)G * slabs, waves)) return;
+  const int lane = lw.lane, k = lane & 31, half = lane >> 5;
+  const int g = (int)(lw.id / slabs);
+  const long sl = lw.id - (long)g * slabs;
+  const long r0 = sl * PROBE_SLAB, r1 = min(N, r0 + PROBE_SLAB);
+  const long base = (long)g * N * 32 + k;
+  double acc = 0.0;
+  for (long r = r0 + half; r < r1; r += 2) {
+    float ro = 0.f, dv = 0.f;
+    if (w[r]) {
+      double rr, dd, ll;
+      probe_logit_terms((double)Z[base + r * 32], (flags[r] >> k) & 1, rr, dd, ll);
+      ro = (float)rr;
+      dv = (float)dd;
+      acc += ll;
+    }
+    R[base + r * 32] = ro;
+    D[base + r * 32] = dv;
+  }
+  acc = probe_join(acc);
+  if (lane < 32) part[lw.id * 32 + lane] = acc;
+}
+
+// The same walk for the eight line-search candidates: part [G, 8, slabs, 32] holds the slab's partial of
+// sum loss(z + 2^-j u, t) (the product 2^-j u is exact in fp64, the sum is rounded once).
+__global__ __launch_bounds__(64 * PROBE_WAVES) void probe_line_kernel(
+    const float* __restrict__ Z, const float* __restrict__ U, const int* __restrict__ flags,
+    const uint8_t* __restrict__ w, int G, long N, long slabs, int waves, double* __restrict__ part) {
+  ListWalk lw;
+  if (!list_walk(lw, (long)G * slabs, waves)) return;
+  const int lane = lw.lane, k = lane & 31, half = lane >> 5;
+  const int g = (int)(lw.id / slabs);
+  const long sl = lw.id - (long)g * slabs;
+  const long r0 = sl * PROBE_SLAB, r1 = min(N, r0 + PROBE_SLAB);
+  const long base = (long)g * N * 32 + k;
+  double acc[PROBE_STEPS];
+#pragma unroll
+  for (int j = 0; j < PROBE_STEPS; ++j) acc[j] = 0.0;
+  for (long r = r0 + half; r < r1; r += 2) {
+    if (!w[r]) continue;
+    const double z = (double)Z[base + r * 32], u = (double)U[base + r * 32];
+    const bool t = (flags[r] >> k) & 1;
+    double s = 1.0;
+#pragma unroll
+    for (int j = 0; j < PROBE_STEPS; ++j) {
+      acc[j] += probe_softplus_loss(z + s * u, t);
+      s *= 0.5;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < PROBE_STEPS; ++j) {
+    const double a = probe_join(acc[j]);
+    if (lane < 32) part[(((long)g * PROBE_STEPS + j) * slabs + sl) * 32 + lane] = a;
+  }
+}
+
 // Four concepts per thread: y <- a x + b y in fp64, one rounding.
 __global__ __launch_bounds__(256) void probe_axpby_kernel(const float* __restrict__ x, const double* __restrict__ a,
                                                           const double* __restrict__ b, int G, long M,
@@ -216,6 +327,49 @@ int sc_probe_rows(const long* row_ptr, const int* col, const float* val, const i
   if (!sc_grid((long)G * N, waves, blocks)) return 1;
   hipLaunchKernelGGL(probe_rows_kernel, dim3(blocks), dim3(64 * waves), 0, stream, row_ptr, col, val, cap, nactive,
                      P, c, w, G, (int)N, n, waves, Q, (unsigned long long*)skipped);
+  return sc_launched();
+}
+
+// sc_probe_rows with every row of Q multiplied by the row of D fp32 [G, N, 32] before the rounding.
+int sc_probe_rows_scaled(const long* row_ptr, const int* col, const float* val, const int* nactive, const float* P,
+                         const double* c, const unsigned char* w, const float* D, float* Q, long* skipped, int G,
+                         long N, int n, long cap, int waves, hipStream_t stream) {
+  if (!row_ptr || !col || !val || !P || !D || !Q || !skipped) return 1;
+  if (G < 1 || N < 1 || N >= 0x7fffffffL || n < 1 || cap < 0 || cap > 0x7fffffffL || !probe_waves_ok(waves)) return 1;
+  unsigned blocks;
+  if (!sc_grid((long)G * N, waves, blocks)) return 1;
+  hipLaunchKernelGGL(probe_rows_scaled_kernel, dim3(blocks), dim3(64 * waves), 0, stream, row_ptr, col, val, cap,
+                     nactive, P, c, w, D, G, (int)N, n, waves, Q, (unsigned long long*)skipped);
+  return sc_launched();
+}
+
+// R, D fp32 [G, N, 32] and loss fp64 [G, 32] from the margins Z fp32 [G, N, 32], the flag words int32 [N] and the
+// fit mask w uint8 [N] (R, D: not Z).  part: fp64 [G, ceil(N / 1024), 32] scratch.
+int sc_probe_logit(const float* Z, const int* flags, const unsigned char* w, float* R, float* D, double* part,
+                   double* loss, int G, long N, int waves, hipStream_t stream) {
+  if (!Z || !flags || !w || !R || !D || !part || !loss) return 1;
+  if (G < 1 || G > 0x3ffffff || N < 1 || N > 0x7fffffffL || !probe_waves_ok(waves)) return 1;
+  const long slabs = (N + PROBE_SLAB - 1) / PROBE_SLAB;
+  unsigned blocks, fold;
+  if (!sc_grid((long)G * slabs, waves, blocks) || !sc_grid((long)G * 32, 64, fold)) return 1;
+  hipLaunchKernelGGL(probe_logit_kernel, dim3(blocks), dim3(64 * waves), 0, stream, Z, flags, w, G, N, slabs, waves,
+                     R, D, part);
+  hipLaunchKernelGGL(probe_dots_fold_kernel, dim3(fold), dim3(64), 0, stream, part, slabs, G, loss);
+  return sc_launched();
+}
+
+// out fp64 [G, 8, 32]: sum over the rows with w != 0 of the loss at Z + 2^-j U, j = 0 .. 7.  part: fp64
+// [G, 8, ceil(N / 1024), 32] scratch.
+int sc_probe_line(const float* Z, const float* U, const int* flags, const unsigned char* w, double* part,
+                  double* out, int G, long N, int waves, hipStream_t stream) {
+  if (!Z || !U || !flags || !w || !part || !out) return 1;
+  if (G < 1 || G > 0x3fffff || N < 1 || N > 0x7fffffffL || !probe_waves_ok(waves)) return 1;
+  const long slabs = (N + PROBE_SLAB - 1) / PROBE_SLAB;
+  unsigned blocks, fold;
+  if (!sc_grid((long)G * slabs, waves, blocks) || !sc_grid((long)G * PROBE_STEPS * 32, 64, fold)) return 1;
+  hipLaunchKernelGGL(probe_line_kernel, dim3(blocks), dim3(64 * waves), 0, stream, Z, U, flags, w, G, N, slabs, waves,
+                     part);
+  hipLaunchKernelGGL(probe_dots_fold_kernel, dim3(fold), dim3(64), 0, stream, part, slabs, G * PROBE_STEPS, out);
   return sc_launched();
 }
 

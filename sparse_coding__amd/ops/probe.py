@@ -19,6 +19,7 @@ CONCEPTS = 32             # columns of every dense operand: one per bit of a fla
 PROBE_SEG = 512           # entries per list segment of ``lists_matmul``: one wave takes one segment (measured:
                           # profiles/r24/probes/README.md; part of the contract, it fixes the fp64 order)
 PROBE_SLAB = 1024         # rows per slab of ``col_dots`` (``csrc/probe.hip``)
+LINE_STEPS = 8            # line-search candidates ``2^-j`` of ``line_losses`` (``csrc/probe.hip``: PROBE_STEPS)
 
 
 def _operand(name: str, t: torch.Tensor, G: int, M: int, dev):
@@ -28,10 +29,13 @@ def _operand(name: str, t: torch.Tensor, G: int, M: int, dev):
 def rows_matmul(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, P: torch.Tensor, *,
                 shift: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                 nactive: Optional[torch.Tensor] = None, skipped: Optional[torch.Tensor] = None,
-                out: Optional[torch.Tensor] = None, waves: Optional[int] = None):
+                out: Optional[torch.Tensor] = None, waves: Optional[int] = None,
+                scale: Optional[torch.Tensor] = None):
     """``Q = C P - 1 (x) shift`` on the rows of ``mask``, zeros on the others: the CSR codes ``row_ptr`` int64
     [G, N + 1], ``col`` int32 / ``val`` fp32 [G, cap] of G models, ``P`` fp32 [G, n, 32], ``shift`` fp64 [G, 32]
     (default: none), ``mask`` uint8 [N] (default: every row).  Returns ``(Q fp32 [G, N, 32], skipped int64 [G])``.
+    ``scale``: fp32 [G, N, 32] (not ``out``); ``Q`` is multiplied by it element by element, in fp64 before the one
+    rounding (``sc_probe_rows_scaled``: the Hessian product of a logistic probe in the same launch).
 
     Per row and concept the products are accumulated in fp64 -- entries 0, 2, 4 .. of the row in one sum, entries
     1, 3, 5 .. in another, each in order, one fma each -- and ``Q`` is the sum of the two, minus the shift, rounded
@@ -57,6 +61,16 @@ def rows_matmul(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, P: 
     (Q,) = out_buffers((("Q", torch.float32, (G, N, CONCEPTS)),), None if out is None else (out,), dev)
     if cap == 0:  # (no entry is stored: only rows 0 .. 0 pass the skip rule and no entry is read)
         col, val = row_ptr.new_zeros(G, 1, dtype=torch.int32), row_ptr.new_zeros(G, 1, dtype=torch.float32)
+    if scale is not None:
+        _operand("scale", scale, G, N, dev)
+        if scale.data_ptr() == Q.data_ptr():
+            raise ValueError("rows_matmul needs scale and out to be different buffers")
+        rc = _lib.lib().sc_probe_rows_scaled(_lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(val), _lib.ptr(nactive),
+                                             _lib.ptr(P), _lib.ptr(shift), _lib.ptr(mask), _lib.ptr(scale),
+                                             _lib.ptr(Q), _lib.ptr(skipped), G, N, n, cap, waves,
+                                             _lib.stream_handle())
+        _lib.check(rc, "sc_probe_rows_scaled")
+        return Q, skipped
     rc = _lib.lib().sc_probe_rows(_lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(val), _lib.ptr(nactive), _lib.ptr(P),
                                   _lib.ptr(shift), _lib.ptr(mask), _lib.ptr(Q), _lib.ptr(skipped), G, N, n, cap,
                                   waves, _lib.stream_handle())
@@ -174,3 +188,58 @@ def axpby_(y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -
     rc = _lib.lib().sc_probe_axpby(_lib.ptr(x), _lib.ptr(a), _lib.ptr(b), _lib.ptr(y), G, M, _lib.stream_handle())
     _lib.check(rc, "sc_probe_axpby")
     return y
+
+
+def _margins(name: str, Z: torch.Tensor, flags: torch.Tensor, mask: torch.Tensor):
+    if Z.dim() != 3:
+        raise ValueError(f"{name} must be fp32 [G, N, {CONCEPTS}]")
+    G, N, dev = Z.shape[0], Z.shape[1], Z.device
+    _operand(name, Z, G, N, dev)
+    _buffer("flags", flags, torch.int32, (N,), dev)
+    _buffer("mask", mask, torch.uint8, (N,), dev)
+    if G < 1 or N < 1 or N > INT32_MAX:
+        raise ValueError(f"the logistic ops need G >= 1 and 1 <= N < 2^31 (got G={G}, N={N})")
+    return G, N, dev
+
+
+def logit_terms(Z: torch.Tensor, flags: torch.Tensor, mask: torch.Tensor, *, out=None, waves: Optional[int] = None):
+    """The terms of a logistic probe at the margins ``Z`` fp32 [G, N, 32]: ``(R fp32 [G, N, 32], D fp32 [G, N, 32],
+    loss fp64 [G, 32])`` with ``R = sigma(Z) - t``, ``D = sigma(Z) (1 - sigma(Z))`` on the rows of ``mask`` (uint8
+    [N]) and zeros on the others, ``t`` bit k of the flag words ``flags`` int32 [N], and ``loss`` the sum over the
+    rows of ``mask`` of ``softplus(z) - t z``, ``softplus(z) = max(z, 0) + log1p(exp(-|z|))``.
+
+    Sigma and the loss are evaluated in fp64 from the fp32 margin -- from ``e = exp(-|z|)`` alone, ``sigma(|z|) =
+    1 / (1 + e)`` and ``sigma(-|z|) = e / (1 + e)`` -- and ``R``, ``D`` are rounded once.  The loss sums are fp64
+    partials over slabs of ``PROBE_SLAB`` rows (even rows of the slab in one sum, odd rows in another, each in
+    order), then the slabs in order, as ``col_dots``.  ``out``: the ``(R, D, loss)`` buffers to fill (not ``Z``).
+    Two launches."""
+    G, N, dev = _margins("Z", Z, flags, mask)
+    waves = check_waves(waves, 4)
+    R, D, loss = out_buffers((("R", torch.float32, (G, N, CONCEPTS)), ("D", torch.float32, (G, N, CONCEPTS)),
+                              ("loss", torch.float64, (G, CONCEPTS))), out, dev)
+    if len({Z.data_ptr(), R.data_ptr(), D.data_ptr()}) != 3:
+        raise ValueError("logit_terms needs Z, R and D to be different buffers")
+    part = torch.empty(G, -(-N // PROBE_SLAB), CONCEPTS, device=dev, dtype=torch.float64)
+    rc = _lib.lib().sc_probe_logit(_lib.ptr(Z), _lib.ptr(flags), _lib.ptr(mask), _lib.ptr(R), _lib.ptr(D),
+                                   _lib.ptr(part), _lib.ptr(loss), G, N, waves, _lib.stream_handle())
+    _lib.check(rc, "sc_probe_logit")
+    return R, D, loss
+
+
+def line_losses(Z: torch.Tensor, U: torch.Tensor, flags: torch.Tensor, mask: torch.Tensor, *,
+                out: Optional[torch.Tensor] = None, waves: Optional[int] = None) -> torch.Tensor:
+    """fp64 [G, 8, 32]: the loss sums of ``logit_terms`` at the margins ``Z + 2^-j U``, j = 0 .. 7 (``Z``, ``U`` fp32
+    [G, N, 32]): the eight candidates of a backtracking line search from one read of ``Z`` and ``U``.  The margin
+    is formed in fp64 (the product with ``2^-j`` is exact, the sum is rounded once); the sums go as in
+    ``logit_terms``.  Two launches."""
+    G, N, dev = _margins("Z", Z, flags, mask)
+    _operand("U", U, G, N, dev)
+    waves = check_waves(waves, 4)
+    if G > 2 ** 22 - 1:
+        raise ValueError(f"line_losses needs G < 2^22 (got {G})")
+    (res,) = out_buffers((("out", torch.float64, (G, LINE_STEPS, CONCEPTS)),), None if out is None else (out,), dev)
+    part = torch.empty(G, LINE_STEPS, -(-N // PROBE_SLAB), CONCEPTS, device=dev, dtype=torch.float64)
+    rc = _lib.lib().sc_probe_line(_lib.ptr(Z), _lib.ptr(U), _lib.ptr(flags), _lib.ptr(mask), _lib.ptr(part),
+                                  _lib.ptr(res), G, N, waves, _lib.stream_handle())
+    _lib.check(rc, "sc_probe_line")
+    return res
